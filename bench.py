@@ -12,6 +12,13 @@ Timing: W warm-up env steps, then `--repeats` windows of exact
 each bracketed by a barrier + device synchronise on both sides and timed as the max over ranks;
 the line reports the median window (all windows listed under "repeats").
 
+A plain run (`--gpus 1 --steps K --warmup W`) does what the headline figure needs and no more: set
+up, warm up, one timed window of K env steps, the result line.  `--full` adds the rest: five
+windows instead of one, the CPU baseline (C3 and C1 on the oracle, ~35 s before the GPU is touched)
+and, with cameras, the render kernel timed on its own.  `--dump-outputs DIR` writes what the last
+timed step left in the env's output buffers as DIR/<name>.npy (float32), for comparing two builds
+on the same seeded inputs.
+
 Multi-GPU: one process per GPU, weak scaling (4096 envs per rank), no data-path collective.
 Under torchrun the ranks come from the environment; `--gpus N` without torchrun starts the N
 rank processes itself (before anything touches a GPU) and relays rank 0's line.  Collectives:
@@ -297,6 +304,27 @@ def binding_roof(pmc: dict | None, workload: str) -> dict | None:
     return out
 
 
+# ----------------------------------------------------------------------------- outputs
+DUMP_IMAGE_ENVS = 32  # envs whose camera images are dumped (2 x S x S x 3 floats each; C5: 12.6 MB)
+
+
+def dump_outputs(env, out_dir: str, rank: int) -> None:
+    """What a caller of the timed path (rollout_expert) finds in the env's buffers after its last env
+    step: the 85-float observation, reward, terminated / truncated / success flags, the staged
+    reward's components and the resident qpos / qvel / ctrl of every env, as float32 .npy files.
+    With cameras, the images of a fixed seeded sample of envs (`image_envs` holds their indices)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"obs": env._obs, "reward": env._reward, "done": env._done, "reward_components": env._rc,
+              "qpos": env.qpos, "qvel": env.qvel, "ctrl": env.ctrl}
+    if env._images is not None:
+        idx = np.sort(np.random.default_rng(0).choice(env.num_envs, min(DUMP_IMAGE_ENVS, env.num_envs), replace=False))
+        arrays["image_envs"] = torch.as_tensor(idx)
+        arrays["images"] = env._images[torch.as_tensor(idx, device=env.device)]
+    suffix = "" if rank == 0 else f".rank{rank}"
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), t.detach().cpu().numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -304,7 +332,12 @@ def main():
     # launch length (16 env steps per launch) keep every timed dispatch the same size
     ap.add_argument("--steps", type=int, default=512)
     ap.add_argument("--warmup", type=int, default=64)
-    ap.add_argument("--repeats", type=int, default=5)
+    # timed windows of --steps env steps each (the line reports the median): 1, or 5 with --full
+    ap.add_argument("--repeats", type=int, default=None)
+    # everything beyond the headline figure: five windows, the CPU baseline, the isolated render timing
+    ap.add_argument("--full", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output buffers of the last timed env step as DIR/<name>.npy")
     ap.add_argument("--envs-per-gpu", type=int, default=4096)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=30.0)
@@ -323,6 +356,8 @@ def main():
     # 128 rows, twelve per CU, above: DESIGN §2); 128 / 192 force one for A/B runs
     ap.add_argument("--step-rows", type=int, default=0, choices=(0, 128, 192))
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     if args.workload == "c5":
         args.image_size = args.image_size or 128
         if args.envs_per_gpu == 4096:
@@ -339,7 +374,7 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: one rank per GPU")
     # CPU baseline first (rank 0 at N = 1): worker processes fork before anything initialises the GPU
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         cpu = cpu_baseline(args.cpu_seconds)
     dist = None
     dev_index = 0 if args.share_device else local_rank
@@ -427,8 +462,10 @@ def main():
                         "rank_kernel_ms": rank_kern_ms, "solver": solver, "rank_envs": env_summary,
                         "episodes": {"completed": int(eps[0]), "successes": int(eps[1]), "placed": int(eps[2]),
                                      "error_resets": int(eps[3]), "envs_with_error_now": int(errs_now)}})
+    if args.dump_outputs:
+        dump_outputs(env, args.dump_outputs, rank)
     isolated = None
-    if args.image_size:
+    if args.full and args.image_size:
         # the render kernel on its own (no step kernels beside it): mmx_forward over the resident
         # states = the position stage (~0.04 ms for 8192 envs) + one render launch over all N envs
         env.sim.forward()

@@ -22,7 +22,7 @@ fi
 for r in $(seq 1 ${ROUNDS:-3}); do for lib in $ALL; do
   n=$(basename $lib .so)
   MMX_LIB_PATH=$lib timeout -k 10 300 python -u bench.py --workload ${WORKLOAD:-c3} --no-cpu-baseline \
-    --steps ${STEPS:-512} --warmup 32 --repeats 1 > $OUT/bench_$n.log 2>&1 || { tail -5 $OUT/bench_$n.log; exit 1; }
+    --steps ${STEPS:-512} --warmup 32 --repeats 1 --full > $OUT/bench_$n.log 2>&1 || { tail -5 $OUT/bench_$n.log; exit 1; }
   echo "$n $(grep -h '^{' $OUT/bench_$n.log)" >> $OUT/ab.txt
 done; done
 if [ "${PMC:-0}" = 1 ]; then
@@ -31,7 +31,7 @@ if [ "${PMC:-0}" = 1 ]; then
     (cd /tmp && export TMPDIR=/tmp && MMX_LIB_PATH=$GRAFT_REPO_ROOT/$lib timeout -s KILL 120 rocprofv3 --pmc \
       SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS \
       SQ_INSTS_LDS SQ_WAIT_INST_LDS --output-format csv -d $OUT/pmc_$n -o run -- python3 $GRAFT_REPO_ROOT/bench.py \
-      --workload ${WORKLOAD:-c3} --steps 32 --warmup 32 --repeats 1 --no-cpu-baseline > $OUT/pmc_$n.log 2>&1) \
+      --workload ${WORKLOAD:-c3} --steps 32 --warmup 32 --repeats 1 --full --no-cpu-baseline > $OUT/pmc_$n.log 2>&1) \
       || { tail -5 $OUT/pmc_$n.log; exit 1; }
   done
 fi

@@ -29,9 +29,9 @@ line() { grep -h '^{' "$1"; }
 bench() {  # bench WL
   local wl=$1 args
   case $wl in
-    c3) args="" ;;
-    driver) args="--gpus 1 --steps 20 --warmup 5 --no-cpu-baseline" ;;
-    c2|c5) args="--workload $wl --no-cpu-baseline" ;;
+    c3) args="--full" ;;
+    driver) args="--gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline" ;;
+    c2|c5) args="--workload $wl --full --no-cpu-baseline" ;;
     *) echo "unknown workload $wl"; return 2 ;;
   esac
   timeout -k 10 400 python -u bench.py $args > gpurun_out/${R}_bench_$wl.log 2>&1 || { tail -5 gpurun_out/${R}_bench_$wl.log; return 1; }
@@ -41,7 +41,7 @@ bench() {  # bench WL
 
 profile() {  # profile WL: trace + separate PMC passes (no trace domain combined with --pmc)
   local wl=$1 out=$ROOT/gpurun_out/prof_$1 steps=${PROF_STEPS:-64} warm=${PROF_WARMUP:-64}
-  local args="--workload $wl --steps $steps --warmup $warm --repeats 1 --no-cpu-baseline"
+  local args="--workload $wl --steps $steps --warmup $warm --repeats 1 --full --no-cpu-baseline"
   rm -rf $out; mkdir -p $out
   (cd /tmp && export TMPDIR=/tmp &&
    timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o run -- \
@@ -69,14 +69,14 @@ trace_driver() {
   local out=$ROOT/gpurun_out/prof_driver
   rm -rf $out; mkdir -p $out
   (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace \
-     -o run -- python3 $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_trace.log 2>&1) || return 1
+     -o run -- python3 $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline > $out/bench_trace.log 2>&1) || return 1
   cp $(find $out/trace -name "*kernel_stats.csv" | head -1) gpurun_out/${R}_driver_kernel_stats.csv
   cp $(find $out/trace -name "*kernel_trace.csv" | head -1) gpurun_out/${R}_driver_kernel_trace.csv
   line $out/bench_trace.log > gpurun_out/${R}_driver_bench_trace.json
 }
 
 render_pmc() {
-  local args="--workload c5 --steps 16 --warmup 4 --repeats 1 --no-cpu-baseline"
+  local args="--workload c5 --steps 16 --warmup 4 --repeats 1 --full --no-cpu-baseline"
   rm -rf $ROOT/gpurun_out/rpmc; mkdir -p $ROOT/gpurun_out/rpmc
   (cd /tmp && export TMPDIR=/tmp &&
    timeout -s KILL 200 rocprofv3 --kernel-include-regex mmx_render_kernel --pmc SQ_WAVE_CYCLES SQ_WAVES SQ_BUSY_CYCLES \

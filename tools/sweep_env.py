@@ -27,7 +27,7 @@ def main():
             for kv in s.split():
                 k, v = kv.split("=", 1)
                 env[k] = v
-            cmd = [sys.executable, "-u", os.path.join(REPO, "bench.py"), "--no-cpu-baseline"] + a.bench_args.split()
+            cmd = [sys.executable, "-u", os.path.join(REPO, "bench.py"), "--full", "--no-cpu-baseline"] + a.bench_args.split()
             p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
             if p.returncode != 0:
                 print(p.stderr[-3000:], file=sys.stderr)
