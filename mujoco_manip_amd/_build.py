@@ -51,8 +51,11 @@ SOURCE_FLAGS = {"mmx_kernels.hip": ["-Xarch_device", "-fassociative-math"],
                 "mmx_step_l192.hip": ["-Xarch_device", "-fassociative-math"]}
 
 
-# test-only builds of the step kernel (tests/test_overflow_kat.py): the same sources with a define that
-# forces a rare path; linked with the product objects of the other sources
+# test-only builds of the step kernel (tests/test_overflow_kat.py, tests/test_helper_layout.py): both
+# step sources (STEP_SOURCES: the 128-row and the 192-row kernel) with defines that force a rare path;
+# linked with the product objects of the other sources
+STEP_SOURCES = ["mmx_kernels.hip", "mmx_step_l192.hip"]
+HIPCC_JOBS = 16  # concurrent hipcc processes of one build()
 TEST_VARIANTS = {
     # a 4-entry collision candidate list (product: 320): the sphere-test overflow path, flagged as
     # ERR_CON_OVERFLOW in env_error
@@ -60,6 +63,11 @@ TEST_VARIANTS = {
     # a 1-entry persistent broadphase list: every collision pass runs the full 780-pair prune (the
     # list-vs-full-prune bit-identity test)
     "libmmx_nolist.so": ["MMX_CAND_CAP=1"],
+    # the 192-row kernel with one of its two waves held back after barriers C and A (MMX_HELPER_DELAY in
+    # mmx_kernels.hip: 1 the helper wave, 2 the env wave), and probe set 14 (full prunes and the list's
+    # displacement bound in the stats): results may not depend on which wave is late
+    "libmmx_hdelay.so": ["MMX_HELPER_DELAY=1", "MMX_PROBE=14"],
+    "libmmx_edelay.so": ["MMX_HELPER_DELAY=2", "MMX_PROBE=14"],
 }
 
 
@@ -91,11 +99,11 @@ def _compile(src: str, profile: bool, verbose: bool) -> str:
     return obj
 
 
-def _compile_test_variant(name: str, verbose: bool) -> str:
+def _compile_test_variant(name: str, src: str, verbose: bool) -> str:
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    obj = os.path.join(CSRC, "mmx_kernels_" + os.path.splitext(name)[0] + ".o")
-    cmd = [hipcc] + FLAGS + SOURCE_FLAGS["mmx_kernels.hip"] + [f"-D{d}" for d in TEST_VARIANTS[name]] + [
-        f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-c", os.path.join(CSRC, "mmx_kernels.hip"), "-o", obj]
+    obj = os.path.join(CSRC, os.path.splitext(src)[0] + "_" + os.path.splitext(name)[0] + ".o")
+    cmd = [hipcc] + FLAGS + SOURCE_FLAGS[src] + [f"-D{d}" for d in TEST_VARIANTS[name]] + [
+        f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-c", os.path.join(CSRC, src), "-o", obj]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
@@ -110,17 +118,19 @@ def build(force: bool = False, verbose: bool = False, profile: bool | None = Fal
     tests = [n for n in TEST_VARIANTS if profile is None and (force or _stale(os.path.join(PKG, n)))]
     if variants or tests:
         jobs = [(src, v) for v in variants for src in SOURCES]
-        with ThreadPoolExecutor(max_workers=len(jobs) + len(tests)) as ex:
-            tobjs = [ex.submit(_compile_test_variant, n, verbose) for n in tests]
+        tjobs = [(n, src) for n in tests for src in STEP_SOURCES]
+        with ThreadPoolExecutor(max_workers=min(HIPCC_JOBS, len(jobs) + len(tjobs))) as ex:
+            tobjs = [ex.submit(_compile_test_variant, n, src, verbose) for n, src in tjobs]
             objs = list(ex.map(lambda j: _compile(j[0], j[1], verbose), jobs))
             tobjs = [f.result() for f in tobjs]
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
         for v in variants:
             mine = [o for o, (_, vv) in zip(objs, jobs) if vv == v]
             subprocess.check_call([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", lib_path(v)] + mine)
-        for n, kobj in zip(tests, tobjs):  # the product's objects of the other sources
-            rest = [os.path.join(CSRC, os.path.splitext(src)[0] + ".o") for src in SOURCES if src != "mmx_kernels.hip"]
-            subprocess.check_call([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", os.path.join(PKG, n), kobj] + rest)
+        for n in tests:  # the variant's step kernels + the product's objects of the other sources
+            kobjs = [o for o, (nn, _) in zip(tobjs, tjobs) if nn == n]
+            rest = [os.path.join(CSRC, os.path.splitext(src)[0] + ".o") for src in SOURCES if src not in STEP_SOURCES]
+            subprocess.check_call([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", os.path.join(PKG, n)] + kobjs + rest)
     return lib_path(bool(profile))
 
 

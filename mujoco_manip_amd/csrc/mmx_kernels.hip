@@ -146,7 +146,7 @@ struct EnvSh {
   // record load invalidates it).
   float cdisp;     // bound on any geom's displacement since the build (x 2: a pair's relative one)
   float crad;      // max over moving geoms of |geom centre - body origin| + bounding radius
-  float cva, cwa;  // this substep's max arm-body origin speed and angular speed (from the RNE)
+  float cspd;      // one-wave build: this substep's max arm-body speed (origin + angular x crad; from the RNE)
   int ncand;
 };
 // The workgroup's env lives in one file-scope LDS object: the non-inlined substep function below
@@ -229,6 +229,31 @@ static_assert(COL_WORK + COL_PLANES * COL_POLY <= COL_END && COL_WORK + MMX_MAXC
 static_assert(SCR_BIAS + 9 <= SCR_FLOATS && SCR_OBS + MMX_NOBS <= SCR_ACT && SCR_ACT + 12 <= SCR_FLOATS &&
                   SCR_EPA + EPA_SCRATCH_FLOATS <= SCR_FLOATS && SCR_IKW + 72 <= SCR_FLOATS,
               "scratch layout");
+// Test builds only (libmmx_hdelay.so / libmmx_edelay.so, tests/test_helper_layout.py): one of the
+// env's two waves is held back right after barriers C and A of every substep (1: the helper wave,
+// before its IK and before its dynamics; 2: the env wave, before its kinematics and before its prune), so
+// whatever one wave reads from LDS while the other writes it shows as a difference between the two
+// builds.  The hold must outlast the longest phase the other wave runs meanwhile: the dynamics, 11.6 k
+// cycles per substep (kinematics 6.0 k, IK 4.2 k: profiles/r06_fsm_profile.json), and twice that for
+// margin is 23 k.  s_sleep waits 64 clocks per unit of its 7-bit operand, so 127 is ~8.1 k clocks and
+// MMX_DELAY_SLEEPS = 4 of them ~32.5 k (~1 M cycles per env step: 16 substeps x 2 holds).  The product
+// build (0) contains none of it.
+#ifndef MMX_HELPER_DELAY
+#define MMX_HELPER_DELAY 0
+#endif
+#if MMX_HELPER_DELAY && MMX_STEP_HELPER
+#define MMX_DELAY_SLEEPS 4
+DEV void delay_wave() {
+#pragma unroll
+  for (int k = 0; k < MMX_DELAY_SLEEPS; k++) __builtin_amdgcn_s_sleep(127);
+  asm volatile("" ::: "memory");  // no LDS access of the phase that follows is moved above the hold
+}
+#define DELAY_HELPER() do { if (MMX_HELPER_DELAY == 1) delay_wave(); } while (0)
+#define DELAY_ENV() do { if (MMX_HELPER_DELAY == 2) delay_wave(); } while (0)
+#else
+#define DELAY_HELPER() do { } while (0)
+#define DELAY_ENV() do { } while (0)
+#endif
 DEV float* scr_of(EnvSh& E) { return reinterpret_cast<float*>(&E.J); }
 DEV const float* scr_of(const EnvSh& E) { return reinterpret_cast<const float*>(&E.J); }
 DEV float* obs_of(EnvSh& E) { return scr_of(E) + SCR_OBS; }
@@ -463,7 +488,10 @@ DEV void kinematics_lane0(EnvSh& E) {
 // transform (static offset x joint), then the chain is composed by pointer jumping (4 rounds
 // cover the 10-deep finger chain): T_b <- T_anc(b) o T_b, anc(b) <- anc(anc(b)).  Cubes read their
 // free joints directly.  Results equal kinematics_lane0 up to fp32 association order.
-DEV void kinematics_wave(EnvSh& E) {
+// in_step (mj_step_wave of the two-wave layout only): workgroup barrier K before the write-out.  The
+// poses written there ARE the IK's kinematics cache (kin_ref), which the helper wave's IK of this substep
+// reads as the previous position stage left it; the helper crosses K once its IK is done.
+DEV void kinematics_wave(EnvSh& E, bool in_step = false) {
   float* T = scr_of(E);  // [12][8] scan scratch: q (4), p (3), ancestor
   const int b = LANE + 1;    // lanes 0..10 -> arm bodies 1..11
   Q4 q = Q4{1.f, 0.f, 0.f, 0.f};
@@ -501,6 +529,9 @@ DEV void kinematics_wave(EnvSh& E) {
     }
     SYNC();
   }
+#if MMX_STEP_HELPER
+  if (in_step) __syncthreads();  // K: the helper's IK has read the cache (uniform: every lane of the env wave)
+#endif
   if (LANE < 11) {
     q = qnormalize(q);
     const M3 R = qmat(q);
@@ -587,13 +618,49 @@ DEV float shr_add_scan(float v) {  // inclusive prefix sum over the lanes of eac
   v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x118, 0xF, 0xF, false));  // row_shr:8
   return v;
 }
+// An arm body's velocity and the speed that enters the broadphase list's displacement bound
+// (list_disp_next), in fmaf with reassociation and contraction off: the 128-row build takes the bound
+// from the RNE's velocities, the two-wave build's env wave computes them itself beside the helper's RNE
+// (arm_body_speed), and the two are separate compiles under -fassociative-math whose bounds, and so
+// their list-use decisions, must agree to the bit.
+DEV SV sv_fma_exact(SV s, float q, SV a) {  // a + s q
+#pragma clang fp reassociate(off) contract(off)
+  return SV{V3{fmaf(s.w.x, q, a.w.x), fmaf(s.w.y, q, a.w.y), fmaf(s.w.z, q, a.w.z)},
+            V3{fmaf(s.v.x, q, a.v.x), fmaf(s.v.y, q, a.v.y), fmaf(s.v.z, q, a.v.z)}};
+}
+// |velocity of the body origin p| + |angular velocity| x crad (vel: world-origin Plucker, v + w x p)
+DEV float body_speed_exact(SV vel, V3 p, float crad) {
+#pragma clang fp reassociate(off) contract(off)
+  const float ox = fmaf(vel.w.y, p.z, fmaf(-vel.w.z, p.y, vel.v.x));
+  const float oy = fmaf(vel.w.z, p.x, fmaf(-vel.w.x, p.z, vel.v.y));
+  const float oz = fmaf(vel.w.x, p.y, fmaf(-vel.w.y, p.x, vel.v.z));
+  return fmaf(sqrtf(fmaf(vel.w.x, vel.w.x, fmaf(vel.w.y, vel.w.y, vel.w.z * vel.w.z))), crad,
+              sqrtf(fmaf(ox, ox, fmaf(oy, oy, oz * oz))));
+}
+#if MMX_STEP_HELPER
+// the env wave's own copy of the RNE's velocity sums (lanes 0..9: the moving arm bodies 11..2)
+DEV float arm_body_speed(const EnvSh& E) {
+  float s = 0.f;
+  if (LANE < 10) {
+    const int b = 11 - LANE;
+    SV vel = SV{V3{0.f, 0.f, 0.f}, V3{0.f, 0.f, 0.f}};
+#pragma unroll
+    for (int d = 0; d < 9; d++)
+      if (arm_anc(d, b)) vel = sv_fma_exact(load_S(E, d), E.qvel[d], vel);
+    s = body_speed_exact(vel, body_x(E, b), E.crad);
+  }
+  return s;
+}
+#endif
 DEV void rne_wave(EnvSh& E) {
   float* F = scr_of(E) + SCR_DYN;
   const int b = 11 - LANE;
   float fi[16];  // the body's force (6), then its inertia (m, h, J: 10)
 #pragma unroll
   for (int m = 0; m < 16; m++) fi[m] = 0.f;
-  float vmax = 0.f, wmax = 0.f;  // for collide_prune's displacement bound
+#if !MMX_STEP_HELPER
+  float spd = 0.f;  // for collide_prune's displacement bound
+#endif
   if (LANE < 10) {
     const RI Ib = body_inertia(E, b);
     SV vel = SV{V3{0.f, 0.f, 0.f}, V3{0.f, 0.f, 0.f}};
@@ -601,14 +668,16 @@ DEV void rne_wave(EnvSh& E) {
 #pragma unroll
     for (int d = 0; d < 9; d++) {
       if (arm_anc(d, b)) {
-        const SV vj = load_S(E, d) * E.qvel[d];
-        acc = acc + cross_motion(vel, vj);
-        vel = vel + vj;
+        const SV Sd = load_S(E, d);
+        const float qd = E.qvel[d];
+        acc = acc + cross_motion(vel, Sd * qd);
+        vel = sv_fma_exact(Sd, qd, vel);
       }
     }
+#if !MMX_STEP_HELPER
+    spd = body_speed_exact(vel, body_x(E, b), E.crad);
+#endif
     const SV f = rimul(Ib, acc) + cross_force(vel, rimul(Ib, vel));
-    vmax = norm(vel.v + cross(vel.w, body_x(E, b)));  // speed of the body origin
-    wmax = norm(vel.w);
     fi[0] = f.w.x; fi[1] = f.w.y; fi[2] = f.w.z; fi[3] = f.v.x; fi[4] = f.v.y; fi[5] = f.v.z;
     ri_store(fi + 6, Ib);
   }
@@ -629,12 +698,10 @@ DEV void rne_wave(EnvSh& E) {
     const float* o = F + 16 * 12 + 6 * MMX_jnt_body[LANE];
     (scr_of(E) + SCR_BIAS)[LANE] = sdot(load_S(E, LANE), SV{V3{o[0], o[1], o[2]}, V3{o[3], o[4], o[5]}});
   }
-  vmax = wave_max(vmax);
-  wmax = wave_max(wmax);
-  if (LANE == 0) {
-    E.cva = vmax;
-    E.cwa = wmax;
-  }
+#if !MMX_STEP_HELPER
+  spd = wave_max(spd);
+  if (LANE == 0) E.cspd = spd;
+#endif
   SYNC();
 }
 
@@ -886,6 +953,24 @@ DEV int wave_compact(bool keep, int* list, int base, int val) {
 // / box lane per pair, box-box one pair per lane quad, GJK/EPA one pair per wave), so lanes of a
 // pass run the same code; (5) deterministic rank sort of the contacts by pair key.  Every prune is
 // conservative, so the contact set equals the all-pairs narrowphase.
+// The persistent list's displacement bound after this substep: E.cdisp + 1.25 x 2 dt x the largest
+// |origin velocity| + |angular velocity| x crad over the moving bodies (+ 1e-5), from qvel and THIS
+// substep's kinematics.  arm: the lane's arm-body speed (body_speed_exact).  The one-wave build passes
+// the RNE's maximum (E.cspd: the dynamics ran before the prune); in the two-wave build the env wave
+// computes the speeds itself (arm_body_speed), so it reads nothing the helper wave writes between
+// barriers A and P.  Lanes 10..12 take the cubes' free joints.  The same bits in both compiles (see
+// sv_fma_exact): the two layouts keep, or rebuild, the list in the same substeps.
+DEV float list_disp_next(const EnvSh& E, float arm) {
+#pragma clang fp reassociate(off) contract(off)
+  float s = arm;
+  if (LANE >= 10 && LANE < 13) {
+    const float* v = E.qvel + 9 + 6 * (LANE - 10);
+    s = fmaf(sqrtf(fmaf(v[3], v[3], fmaf(v[4], v[4], v[5] * v[5]))), E.crad,
+             sqrtf(fmaf(v[0], v[0], fmaf(v[1], v[1], v[2] * v[2]))));
+  }
+  return E.cdisp + fmaf(1.25f * 2.f * kDt, wave_max(s), 1e-5f);
+}
+
 DEV void collide_prune(EnvSh& E, bool only_ro) {
   float* stats = E.stats;
   CLK_DECL;
@@ -898,23 +983,19 @@ DEV void collide_prune(EnvSh& E, bool only_ro) {
   int* cand = reinterpret_cast<int*>(scr + COL_CAND);
   // (2) runs over the persistent list when it is still valid: its pairs were within
   // MMX_CAND_MARGIN of contact at the build, and no pair has since closed by more than the bound
-  // cdisp = sum over substeps of 2 dt (max body-origin speed + max angular speed x crad) (x 1.25
-  // for the integrators' second-order terms).  The list is in pair order, so the exact test below
+  // cdisp = sum over substeps of 2 dt max over bodies (origin speed + angular speed x crad) (x 1.25
+  // for the integrators' second-order terms; list_disp_next).  The list is in pair order, so the exact test below
   // keeps the same candidates, in the same order, as the all-pairs pass.
   bool use_list = false;
   if (!only_ro && E.ncand >= 0) {
-    float vc = 0.f;
-    if (LANE < 3) {
-      const int da = 9 + 6 * LANE;
-      vc = norm(V3{E.qvel[da], E.qvel[da + 1], E.qvel[da + 2]}) +
-           norm(V3{E.qvel[da + 3], E.qvel[da + 4], E.qvel[da + 5]}) * E.crad;
-    }
-    vc = fmaxf(fmaxf(readlane_max0(vc), __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vc), 1))),
-               __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vc), 2)));
-    const float inc = 1.25f * 2.f * kDt * fmaxf(fmaf(E.cwa, E.crad, E.cva), vc) + 1e-5f;
-    use_list = E.cdisp + inc < 0.5f * MMX_CAND_MARGIN;
+#if MMX_STEP_HELPER
+    const float nd = list_disp_next(E, arm_body_speed(E));
+#else
+    const float nd = list_disp_next(E, LANE < 10 ? E.cspd : 0.f);
+#endif
+    use_list = nd < 0.5f * MMX_CAND_MARGIN;
     SYNC();
-    if (LANE == 0) E.cdisp = use_list ? E.cdisp + inc : E.cdisp;
+    if (LANE == 0 && use_list) E.cdisp = nd;
   }
   const bool rebuild = !only_ro && !use_list;
   if (LANE < MMX_NGEOM) {
@@ -1073,6 +1154,12 @@ DEV void collide_prune(EnvSh& E, bool only_ro) {
     stats[STAT_T_AUX1] += (rebuild && E.ncand < 0) ? 1.f : 0.f;
     stats[STAT_T_AUX2] += (float)ncls[1];
     stats[STAT_T_AUX3] += (float)ncls[2];
+  }
+  // probe set 14 (the delay builds; no phase clock needed): the full prunes, and the list's displacement
+  // bound as this pass leaves it, so the list-use decisions and the speeds they used show in the stats
+  if (MMX_PROBE == 14 && LANE == 0 && !only_ro) {
+    stats[STAT_T_AUX0] += use_list ? 0.f : 1.f;
+    stats[STAT_T_AUX1] = E.cdisp;
   }
   PROBE(2, stats, STAT_T_AUX2);
   PROBE(5, stats, STAT_T_AUX3);
@@ -2552,11 +2639,22 @@ DEV void mj_step_wave(int max_iter, float tol, EnvSh& E, float* con_dst) {
   float* stats = E.stats;
   CLK_DECL;
 #if MMX_STEP_HELPER
-  // the env wave and the helper wave (the kernel's helper loop mirrors these workgroup barriers)
+  // the env wave and the helper wave (the kernel's helper loop mirrors these workgroup barriers: C, K,
+  // A, P, Q in every substep, no path of either wave skips one).  Between two barriers the waves share
+  // LDS read-only, or write disjoint parts of it:
+  //   C..K  env: the chain scan in its scratch        helper: the IK (reads the kinematics cache = the
+  //                                                   previous position stage's poses; writes ctrl)
+  //   K..A  env: writes the poses and S (the cache)   helper: nothing
+  //   A..P  env: the prune (reads poses, S, qvel;     helper: the dynamics (reads the same; writes M9,
+  //         its displacement bound is its own)        qfrc, qacc_s and its scratch)
+  //   P..Q  env: plane and box-box pairs              helper: the GJK / EPA pairs
+  // (tests/test_helper_layout.py holds either wave back after C and A and compares the results)
   __syncthreads();  // C: the previous substep's state is in LDS; the helper runs the IK
-  kinematics_wave(E);
+  DELAY_ENV();
+  kinematics_wave(E, true);  // (barrier K inside, before the poses are written)
   CLK(stats, STAT_T_KIN);
   __syncthreads();  // A: the kinematics; the helper runs the dynamics beside the broadphase
+  DELAY_ENV();
   collide_prune(E, false);
   __syncthreads();  // P: the class lists (and the dynamics); the helper takes the GJK / EPA pairs
   collide_pairs(E, false, 1);
@@ -3000,8 +3098,6 @@ DEV void load_env(const MMXState& S, int i, EnvSh& E) {
     E.nefc = 0;
     E.nefc_mj = 0;
     E.ncand = -1;  // positions come from the record: rebuild the broadphase list
-    E.cva = 3e38f;
-    E.cwa = 3e38f;
   }
   SYNC();
 }
@@ -3250,10 +3346,13 @@ MMX_STEP_SYM(mmx_env_step_kernel)(MMXState S, const float* action, int adim, int
         XSYNC();
       }
       XSYNC();  // step_begin's record load
-      for (int sub = 0; sub < MMX_NSUBSTEP; sub++) {  // mj_step_wave's barriers C, A, P, Q
+      for (int sub = 0; sub < MMX_NSUBSTEP; sub++) {  // mj_step_wave's barriers C, K, A, P, Q
         __syncthreads();
+        DELAY_HELPER();
         ik_wave(g_E);
+        __syncthreads();  // K: the IK has read the kinematics cache; the env wave may overwrite it
         __syncthreads();
+        DELAY_HELPER();
         dynamics_wave(g_E);
         __syncthreads();
         collide_pairs(g_E, false, 2);

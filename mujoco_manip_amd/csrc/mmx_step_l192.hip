@@ -4,7 +4,8 @@
 // batch fills the workgroup slots; with four or fewer envs per CU each env's own speed is what counts
 // and this one is faster (C2's 1024 envs: 1.52 M vs 1.29 M env steps/s).  mmx_api.cpp picks
 // per sim from the batch size (mmx_set_step_rows, include/mmx_tuning.h).  Same sources, same arithmetic, bit-identical results: only where the rows past
-// the LDS ones live and the register budget differ.
+// the LDS ones live and the register budget differ, and the two waves are ordered by workgroup barriers
+// wherever one writes what the other reads (mj_step_wave; tests/test_helper_layout.py delays either).
 #undef MMX_LDSEFC
 #define MMX_LDSEFC 192
 #define MMX_STEP_ONLY 1

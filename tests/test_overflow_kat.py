@@ -1,6 +1,7 @@
 """Collision candidate tests with test-only builds (_build.TEST_VARIANTS), each run in a child process
-because the binding loads one library per process.  The test builds recompile the 128-row kernel only
-(their 192-row kernel is the product's), so the children pin the 128-row layout (MMX_STEP_ROWS).
+because the binding loads one library per process.  The test builds compile both step kernels with their
+defines, and every test with a test build runs on both layouts (MMX_STEP_ROWS: 128 rows, and the 192 rows
+with a helper wave that small batches get).
 
 * Contact-overflow KAT: more sphere-test survivors than the candidate list holds must reach
   env_error as ERR_CON_OVERFLOW, whichever substep of the env step overflowed (the flag is sticky from
@@ -38,12 +39,13 @@ print("OVERFLOW_ENVS", int(hit.sum()), "NAN_ENVS", int(((env.env_error.cpu().num
 """
 
 
-def test_candidate_list_overflow_reaches_env_error():
+@pytest.mark.parametrize("rows", [128, 192])
+def test_candidate_list_overflow_reaches_env_error(rows):
     if not torch.cuda.is_available():
         pytest.skip("needs an MI355X")
     lib = os.path.join(REPO, "mujoco_manip_amd", "libmmx_col4.so")
     assert os.path.exists(lib), "test build missing: run __graft_entry__.build()"
-    r = subprocess.run([sys.executable, "-c", CHILD, REPO], env=dict(os.environ, MMX_LIB_PATH=lib, MMX_STEP_ROWS="128"),
+    r = subprocess.run([sys.executable, "-c", CHILD, REPO], env=dict(os.environ, MMX_LIB_PATH=lib, MMX_STEP_ROWS=str(rows)),
                        capture_output=True,
                        text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -78,7 +80,7 @@ import torch
 import oracle_py as O
 from mujoco_manip_amd import _lib
 from mujoco_manip_amd.vec_env import PickPlaceVecEnv
-n = 512
+n = int(sys.argv[2])
 env = PickPlaceVecEnv(n, tasks="all", action_mode="abs_pos", reward_type="staged", randomize_objects=True,
                       autoreset=True, image_size=0)
 env.reset(seed=[O.episode_seed(42, i) for i in range(n)])
@@ -96,20 +98,24 @@ print("PHASES", " ".join(str(p) for p in sorted(phases)))
 """
 
 
-def test_broadphase_list_equals_full_prune():
+@pytest.mark.parametrize("rows", [128, 192])
+def test_broadphase_list_equals_full_prune(rows):
     """the persistent broadphase list (the pairs within 8 cm of contact when it was
     built, kept while the bodies' displacement bound stays under half of that) gives the same
-    candidates, in the same order, as the full 780-pair prune.  512 C3 envs for 90 env steps (approach,
-    grasp, transport, release, retreat): the product library (a 256-entry list) and the test build
+    candidates, in the same order, as the full 780-pair prune.  512 C3 envs (256 on the 192-row layout: the
+    smallest batch that still reaches the last phases) for 90 env steps (approach, grasp, transport,
+    release, retreat): the product library (a 256-entry list) and the test build
     libmmx_nolist.so (a 1-entry list: the full prune in every collision pass) end every 10-step block
     with bit-identical states and last-substep contact lists."""
     if not torch.cuda.is_available():
         pytest.skip("needs an MI355X")
     res = []
+    n = 512 if rows == 128 else 256
     for lib in ("libmmx.so", "libmmx_nolist.so"):
         path = os.path.join(REPO, "mujoco_manip_amd", lib)
         assert os.path.exists(path), "test build missing: run __graft_entry__.build()"
-        r = subprocess.run([sys.executable, "-c", CHILD_DIGEST, REPO], env=dict(os.environ, MMX_LIB_PATH=path, MMX_STEP_ROWS="128"),
+        r = subprocess.run([sys.executable, "-c", CHILD_DIGEST, REPO, str(n)],
+                           env=dict(os.environ, MMX_LIB_PATH=path, MMX_STEP_ROWS=str(rows)),
                            capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]
         lines = {ln.split()[0]: ln.split()[1:] for ln in r.stdout.splitlines() if ln.startswith(("DIGESTS", "PHASES"))}
