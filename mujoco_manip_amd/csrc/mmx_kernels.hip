@@ -35,10 +35,13 @@
 // lane within the wave (a workgroup is one wave: one env)
 // Lane id re-materialised per use (an opaque copy of threadIdx.x): nothing lane-derived (lane masks,
 // per-lane dof / row indices) is hoisted to a function's entry and kept live across it.  In the
-// Newton solver, where the substep's register peak sits, that frees registers: the substep's
-// callee-saved save area 592 -> 436 B per lane and most SGPR spills go, for fewer instructions
-// overall (C3 +2.4 % in the A/B); applied everywhere it costs more re-materialisation than it saves
-// (-0.6 %), and in the constraint / collision / integrate + IK sections as well -0.8 to -1.7 %.
+// Newton solver, where the substep's register peak sits, that frees registers.  When adopted (C3
+// +2.4 %) it counted for the callee-saved save area the substep then had (592 -> 436 B per lane); the
+// substep saves nothing for its caller now (MMX_NO_TAIL_MARK) and the copy still pays, through the
+// substep's own spills: with the plain lane id 35 scratch stores / 48 loads and 315 SGPR-spill
+// writelanes against 6 / 9 and 101 (128-row build), C3 -10.4 % (profiles/r07_ab_nocsr.json).  Applied
+// everywhere it costs more re-materialisation than it saves (-0.6 %), and in the constraint /
+// collision / integrate + IK sections as well -0.8 to -1.7 %.
 DEV int lane_opaque() {
   int t = (int)threadIdx.x;
   asm volatile("" : "+v"(t));
@@ -1733,8 +1736,9 @@ DEV void tile_gather(const float* G, int t, int bd, int od, float* hrow, float& 
     gacc += Gr[15];
   }
 }
-// row types staged per barrier round (E.con holds up to three 16 x 16 tiles; 3 measured -1.3 % in the
-// r03 A/B: the unrolled rounds grow the substep's register save area)
+// row types staged per barrier round.  3 measured -1.3 % in the r03 A/B, when E.con held three
+// 16 x 16 tiles and the unrolled rounds grew the register save area the substep then had; since the
+// LDS shrink E.con (MMX_MAXCON * CL_F = 512 floats) holds one tile of 16 * GST = 272, so only 1 builds
 #define HESS_TILES 1
 static_assert(HESS_TILES * 16 * GST <= MMX_MAXCON * CL_F, "Hessian staging tiles exceed E.con");
 DEV float hess_grad_mfma(EnvSh& E, int nefc, float* hrow, float mdx) {
@@ -2155,7 +2159,10 @@ DEV float chol_solve_arrow(EnvSh& E, const float* hrow, float v, int cpl) {
   return j >= 0 ? y : 0.f;
 }
 
-// H^{-1} v: the block form unless two cubes are coupled (a cube resting on or pushing another)
+// H^{-1} v: the block form unless two cubes are coupled (a cube resting on or pushing another).
+// The general solve stays inline although C3 never runs it: out of line (its Hessian row passed by
+// value, no register save on either side) the kernel is ~3,100 instructions shorter but no faster
+// (-0.01 % on the medians, the spread 0.3 %: profiles/r07_ab_nocsr.json).
 DEV float chol_solve(EnvSh& E, const float* hrow, float v, int cpl) {
   float* stats = E.stats;
   CLK_DECL;
@@ -3251,7 +3258,16 @@ extern "C" __global__ void __launch_bounds__(WG) mmx_substep_kernel(MMXState S, 
 
 // One substep = IK + mj_step, kept out of line: nothing is hoisted across the 16 iterations of
 // the env-step loop (hoisted invariants would pin registers for the whole kernel and serialise
-// the phases' LDS loads); the price is the callee-saved register spill / fill per call.
+// the phases' LDS loads).  The call costs no register save: substep, step_begin and step_finish
+// have local linkage after the device link's internalisation, do not recurse and never have their
+// address taken, so the AMDGPU backend compiles them without callee-saved registers -- provided no
+// call site of theirs carries the IR `tail` marker, which the optimiser stamps on any call that does
+// not touch the caller's stack, and which alone switches that path off.  MMX_NO_TAIL_MARK on the
+// caller keeps the marker away; every function that calls one of the three needs it (one marked site
+// brings the saves back: at the 168-VGPR cap 64 VGPRs stored and reloaded per call, 16 KB per wave,
+// 16 calls per env step, which was 178 KB of HBM writes per env step).  The caller instead keeps
+// its own few live values (env index, loop counters, pointers) in SGPRs / reloads them after a call.
+#define MMX_NO_TAIL_MARK __attribute__((disable_tail_calls))
 //
 // (Measured and removed: splitting one env over two waves, wave 1 running the collision prune and
 // the plane / box-box pairs beside wave 0's dynamics and GJK/EPA: register-bound at 4 workgroups per
@@ -3275,7 +3291,8 @@ __device__ __attribute__((noinline)) void substep(int max_iter, float tol, float
 // bit-identical to nsteps single-step launches, minus nsteps - 1 launch tails.
 // The step's prologue (record load, FSM plan, action decode) and epilogue (position stage, reward,
 // observation, autoreset, record store) are out of line like the substep: inlined into the fused
-// step loop they kept ~280 VGPRs of hoisted values live across iterations (scratch spills).
+// step loop they kept ~280 VGPRs of hoisted values live across iterations (scratch spills).  Like
+// the substep they save no registers for their caller (MMX_NO_TAIL_MARK on the kernel).
 __device__ __attribute__((noinline)) void step_begin(const MMXState& S, int i, const float* action, int adim,
                                                      int expert) {
   EnvSh& E = g_E;
@@ -3333,7 +3350,7 @@ extern "C" int mmx_fsm_profile_fields() { return FSMP_N; }
 #define MMX_CAT_(a, b) MMX_CAT2_(a, b)
 #define MMX_STEP_SYM(name) MMX_CAT_(name, MMX_STEP_SUFFIX)
 extern "C" __global__ void __launch_bounds__(MMX_STEP_THREADS) __attribute__((amdgpu_waves_per_eu(MMX_STEP_WAVES, MMX_STEP_WAVES)))
-MMX_STEP_SYM(mmx_env_step_kernel)(MMXState S, const float* action, int adim, int expert, int base, int nsteps,
+MMX_NO_TAIL_MARK MMX_STEP_SYM(mmx_env_step_kernel)(MMXState S, const float* action, int adim, int expert, int base, int nsteps,
                                   const int* order) {
   // order (optional): the launch's envs in dispatch order, the grasp-carrying ones first (mmx_order_kernel)
   const int i = order ? order[blockIdx.x] : base + blockIdx.x;
