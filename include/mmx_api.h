@@ -187,6 +187,19 @@ int mmx_expert_physics(mmx_sim* sim, int32_t n_physics_steps);
 int mmx_eval_reward(mmx_sim* sim, const float* obj_dev, const float* ee_dev, const float* ctrl7_dev,
                     const int32_t* pairs_dev, int32_t max_pairs);
 
+/* Opt-in camera effects (off by default: the images are then exactly what they were without this
+ * call).  MMX_RENDER_SHADOWS: the scene's directional light (dir 0 0 -1, castshadow) casts shadows: a
+ * surface point loses the light's term where an opaque, non-floor surface lies above it (a per-env
+ * height map, 130 KB per env, allocated at the first call that asks for it).  MMX_RENDER_TRANSLUCENT:
+ * the three bins are blended at their material alpha 0.4 over what lies behind them, every layer.
+ * Segment ids do not change.  mmx_set_render_effects takes a mask of the flags and takes effect from
+ * the next render (reset / step / forward / rollout); it does not render by itself.  MMX_EINVAL for
+ * unknown bits or a sim without cameras (image_size == 0); MMX_ENOMEM when the map cannot be
+ * allocated (the previous flags stay).  mmx_get_render_effects returns the mask (0 for a NULL sim). */
+enum { MMX_RENDER_SHADOWS = 1, MMX_RENDER_TRANSLUCENT = 2 };
+int mmx_set_render_effects(mmx_sim* sim, int32_t flags);
+int mmx_get_render_effects(const mmx_sim* sim);
+
 int mmx_get_buffers(mmx_sim* sim, mmx_buffers* out);
 /* Waits for the sim's stream; MMX_ESAMPLING when an autoreset since the last check (mmx_reset or
  * mmx_synchronize) exhausted its spawn sampling (that env's env_error has bit 8). */

@@ -32,6 +32,20 @@ STAT_FIELDS = ("sum_nefc", "sum_ncon", "sum_solver_iter", "substeps", "max_resid
 ACTION_MODES = ("abs_pos", "ee_pos_quat_g", "ee_pos_rot6d_g", "ee_pos_quat_g_rel", "ee_pos_rot6d_g_rel")
 ACTION_DIMS = (4, 8, 10, 8, 10)
 REWARD_TYPES = ("dense", "sparse", "staged")
+# opt-in camera effects (include/mmx_api.h MMX_RENDER_SHADOWS, MMX_RENDER_TRANSLUCENT)
+RENDER_EFFECTS = {"shadows": 1, "translucent_bins": 2}
+
+
+def render_effect_flags(effects) -> int:
+    """The flag mask of a tuple of effect names ("shadows", "translucent_bins"); () = 0."""
+    if isinstance(effects, str):
+        effects = (effects,)
+    flags = 0
+    for e in effects or ():
+        if e not in RENDER_EFFECTS:
+            raise ValueError(f"render_effects entries must be among {tuple(RENDER_EFFECTS)}, got '{e}'")
+        flags |= RENDER_EFFECTS[e]
+    return flags
 
 
 class MMXConfig(C.Structure):
@@ -62,7 +76,8 @@ EXPORTED = ("mmx_config_default", "mmx_create", "mmx_destroy", "mmx_last_error",
             "mmx_rollout_steps_per_launch", "mmx_rollout_launches", "mmx_expert_physics", "mmx_eval_reward", "mmx_kernel_timing",
             "mmx_kernel_times", "mmx_png_bound", "mmx_png_scratch", "mmx_png_encode", "mmx_png_pack", "mmx_image_stats",
             "mmx_queue_init", "mmx_queue_advance", "mmx_set_step_rows", "mmx_step_rows", "mmx_copy_ranges", "mmx_rollout_render_launches",
-            "mmx_set_step_order", "mmx_step_order", "mmx_rollout_render_overlap")
+            "mmx_set_step_order", "mmx_step_order", "mmx_rollout_render_overlap", "mmx_set_render_effects",
+            "mmx_get_render_effects")
 
 _lib = None
 
@@ -104,6 +119,9 @@ def load(build_if_missing: bool = True):
     L.mmx_rollout_render_overlap.argtypes = [vp]
     L.mmx_rollout_render_overlap.restype = C.c_int
     L.mmx_step_order.argtypes = [vp]
+    L.mmx_set_render_effects.argtypes = [vp, C.c_int32]
+    L.mmx_get_render_effects.argtypes = [vp]
+    L.mmx_get_render_effects.restype = C.c_int
     L.mmx_step_order.restype = C.c_int
     L.mmx_rollout_steps_per_launch.argtypes = [vp]
     L.mmx_rollout_steps_per_launch.restype = C.c_int
@@ -132,7 +150,8 @@ def load(build_if_missing: bool = True):
     for name in ("mmx_create", "mmx_reset", "mmx_step", "mmx_expert_plan", "mmx_rollout_expert", "mmx_physics_step",
                  "mmx_forward", "mmx_get_buffers", "mmx_synchronize", "mmx_get_state", "mmx_set_state",
                  "mmx_expert_physics", "mmx_eval_reward", "mmx_kernel_timing", "mmx_kernel_times", "mmx_png_encode",
-                 "mmx_png_pack", "mmx_image_stats", "mmx_queue_init", "mmx_queue_advance", "mmx_set_step_rows", "mmx_set_step_order"):
+                 "mmx_png_pack", "mmx_image_stats", "mmx_queue_init", "mmx_queue_advance", "mmx_set_step_rows", "mmx_set_step_order",
+                 "mmx_set_render_effects"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -163,7 +182,10 @@ class Sim:
                  max_episode_steps: int = 500, randomize_objects: bool = False,
                  spawn_x_range=(-0.20, 0.20), spawn_y_range=(0.30, 0.45), task_pool=None, fixed_task=None,
                  image_size: int = 224, autoreset: bool = False, solver_iterations: int = 30,
-                 solver_tolerance: float = 1e-6, device: int = 0, stream: int | None = None):
+                 solver_tolerance: float = 1e-6, device: int = 0, stream: int | None = None, render_effects=()):
+        effects = render_effect_flags(render_effects)
+        if effects and int(image_size) <= 0:
+            raise ValueError("render_effects need cameras (image_size > 0)")
         if action_mode not in ACTION_MODES:
             raise ValueError(f"action_mode must be one of {ACTION_MODES}, got '{action_mode}'")
         if reward_type not in REWARD_TYPES:
@@ -204,6 +226,8 @@ class Sim:
         self.ptr = ptr
         self.buffers = MMXBuffers()
         self._check(self.L.mmx_get_buffers(self.ptr, C.byref(self.buffers)), "mmx_get_buffers")
+        if effects:  # before the first reset renders
+            self.render_effects = effects
 
     def _check(self, rc, what):
         if rc == MMX_ESAMPLING:  # the reference's own exception and message (randomization.py:84-87)
@@ -416,6 +440,18 @@ class Sim:
     @step_rows.setter
     def step_rows(self, rows: int):
         self._check(self.L.mmx_set_step_rows(self.ptr, int(rows)), "mmx_set_step_rows")
+
+    @property
+    def render_effects(self) -> int:
+        """Flag mask of the opt-in camera effects (RENDER_EFFECTS: cast shadows, translucent bins; 0 =
+        the default flat images).  Setting it takes effect from the next render."""
+        return int(self.L.mmx_get_render_effects(self.ptr))
+
+    @render_effects.setter
+    def render_effects(self, flags):
+        if not isinstance(flags, int):
+            flags = render_effect_flags(flags)
+        self._check(self.L.mmx_set_render_effects(self.ptr, int(flags)), "mmx_set_render_effects")
 
     @property
     def rollout_render_overlap(self) -> bool:

@@ -30,6 +30,8 @@ extern "C" hipError_t mmx_launch_render(const MMXState* S, int base, int count, 
 extern "C" hipError_t mmx_launch_render_bg(const MMXState* S, hipStream_t st);
 extern "C" hipError_t mmx_launch_render_masked(const MMXState* S, int base, int count, const unsigned char* mask,
                                                hipStream_t st);
+extern "C" void mmx_render_effects_bind(const MMXState* S, int flags, unsigned short* shmap);
+extern "C" size_t mmx_render_shadow_map_bytes();
 extern "C" hipError_t mmx_launch_queue(const MMXState* S, int* slot, int* next, int n_ep, const unsigned long long* rng,
                                        const int* qtask, unsigned char* mask, int* task, int* slot_out, int* fin_out,
                                        hipStream_t st);
@@ -80,6 +82,10 @@ struct mmx_sim {
   float* rpose_alt = nullptr;
   hipStream_t rstream = nullptr;
   hipEvent_t ev_step = nullptr, ev_rend[2] = {};
+  // opt-in render effects (mmx_set_render_effects): the flags and the per-env shadow height maps
+  // (allocated when shadows are first asked for); mmx_render.hip keeps them under S.images
+  int render_effects = 0;
+  unsigned short* shmap = nullptr;
   // per-launch kernel timing (mmx_kernel_timing): an event pair around every step / render launch
   // on the stream it runs on; pairs come from a pool reused after each read-out
   bool timing = false;
@@ -410,6 +416,7 @@ void mmx_destroy(mmx_sim* sim) {
   if (!sim) return;
   DeviceGuard guard(sim);
   (void)hipDeviceSynchronize();
+  if (sim->render_effects) mmx_render_effects_bind(&sim->S, 0, nullptr);
   for (void* p : sim->allocs)
     if (p) (void)hipFree(p);
   for (int l = 1; l < sim->nlanes; l++) {
@@ -787,6 +794,22 @@ int mmx_forward(mmx_sim* sim) {
   if (e == hipSuccess) e = mmx_launch_render(&sim->S, 0, sim->S.N, sim->stream);
   return hip_check(sim, e, "mmx_forward");
 }
+
+int mmx_set_render_effects(mmx_sim* sim, int32_t flags) {
+  if (!sim) return MMX_EINVAL;
+  if (flags & ~(MMX_RENDER_SHADOWS | MMX_RENDER_TRANSLUCENT)) return fail(sim, MMX_EINVAL, "mmx_set_render_effects: unknown flag bits");
+  if (sim->S.image_size <= 0) return fail(sim, MMX_EINVAL, "mmx_set_render_effects: the sim has no cameras (image_size = 0)");
+  DeviceGuard guard(sim);
+  if ((flags & MMX_RENDER_SHADOWS) && !sim->shmap) {
+    const size_t per_env = mmx_render_shadow_map_bytes() / sizeof(unsigned short);
+    sim->shmap = dalloc<unsigned short>(sim, per_env * static_cast<size_t>(sim->S.N));
+    if (!sim->shmap) return fail(sim, MMX_ENOMEM, "mmx_set_render_effects: shadow maps");
+  }
+  sim->render_effects = flags;
+  mmx_render_effects_bind(&sim->S, flags, sim->shmap);
+  return MMX_OK;
+}
+int mmx_get_render_effects(const mmx_sim* sim) { return sim ? sim->render_effects : 0; }
 
 int mmx_get_buffers(mmx_sim* sim, mmx_buffers* b) {
   if (!sim || !b) return MMX_EINVAL;

@@ -20,12 +20,23 @@
 //      flat per-face light, MuJoCo's headlight (ambient 0.3, diffuse 0.6) + the scene's directional
 //      (0.8) and point (0.4) lights (pick_and_place_scene.xml:6-9,33-36), the floor checker (0.1 m
 //      squares), sky gradient elsewhere; RGB u8 and the segment id written as packed dwords.
-// Not modelled (documented in DESIGN.md): shadows, specular, reflectance, bin transparency
+// Not modelled by default (documented in DESIGN.md): shadows, specular, reflectance, bin transparency
 // (alpha 0.4 -> opaque); the Panda's visual meshes are reduced per part (tools/compile_render.py:
 // convex pieces for the links, clustered hand / fingers; robot-mask IoU vs the full meshes in
 // tests/test_render.py).
+// Opt-in effects (mmx_set_render_effects): this file compiled a second time with MMR_LIT
+// (mmx_render_lit.hip) gives mmx_render_lit_kernel, the same rasteriser with cast shadows of the
+// directional light (a per-env height map, mmx_shadow_kernel) and the bins blended at alpha 0.4; the
+// flat kernel below is what every sim runs until it asks for an effect.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <atomic>
+#include <mutex>
+#include <vector>
+#ifndef MMR_LIT
+#define MMR_LIT 0
+#endif
 
 #define MMX_MODEL_QUAL static __constant__
 #include "mmx_model_gen.h"
@@ -238,18 +249,9 @@ DEV void rays4(int px0, int py, float half, float f, const M3& cR, V3* dw4) {
   V3 dw = mul(cR, V3{(px0 + 0.5f - half) * rf, -(py + 0.5f - half) * rf, -1.f});
   for (int u = 0; u < 4; u++, dw = dw + dx) dw4[u] = dw;
 }
-// bg: the camera's precomputed background row (fixed cameras), or null (computed per pixel)
-DEV void shade4(const uint32_t* keys, int px0, int py, float half, float f, const M3& cR, const V3& cx,
-                float floor_light0, const uint32_t* tinfo, const float* mrgb, const uint32_t* bg, uint32_t* rgb_out,
-                uint32_t* seg_out, int nvalid) {
-  uint32_t pix[4];
-  if (bg) {
-    for (int u = 0; u < 4; u++) pix[u] = keys[u] != 0u ? tinfo[keys[u] & 4095] : bg[px0 + u];
-  } else {
-    V3 dw4[4];
-    rays4(px0, py, half, f, cR, dw4);
-    for (int u = 0; u < 4; u++) pix[u] = keys[u] != 0u ? tinfo[keys[u] & 4095] : shade_bg(dw4[u], cx, floor_light0, mrgb);
-  }
+// 4 horizontally adjacent packed pixels (rend_pack) to the image: RGB u8 (3 dwords) and segment ids
+// (1 dword)
+DEV void rend_store4(const uint32_t* pix, uint32_t* rgb_out, uint32_t* seg_out, int nvalid) {
   const uint32_t rgbw[3] = {(pix[0] & 0xFFFFFFu) | (pix[1] << 24), ((pix[1] >> 8) & 0xFFFFu) | (pix[2] << 16),
                             ((pix[2] >> 16) & 0xFFu) | (pix[3] << 8)};
   const uint32_t segw = (pix[0] >> 24) | ((pix[1] >> 24) << 8) | ((pix[2] >> 24) << 16) | (pix[3] & 0xFF000000u);
@@ -265,9 +267,127 @@ DEV void shade4(const uint32_t* keys, int px0, int py, float half, float f, cons
     }
   }
 }
+// bg: the camera's precomputed background row (fixed cameras), or null (computed per pixel)
+DEV void shade4(const uint32_t* keys, int px0, int py, float half, float f, const M3& cR, const V3& cx,
+                float floor_light0, const uint32_t* tinfo, const float* mrgb, const uint32_t* bg, uint32_t* rgb_out,
+                uint32_t* seg_out, int nvalid) {
+  uint32_t pix[4];
+  if (bg) {
+    for (int u = 0; u < 4; u++) pix[u] = keys[u] != 0u ? tinfo[keys[u] & 4095] : bg[px0 + u];
+  } else {
+    V3 dw4[4];
+    rays4(px0, py, half, f, cR, dw4);
+    for (int u = 0; u < 4; u++) pix[u] = keys[u] != 0u ? tinfo[keys[u] & 4095] : shade_bg(dw4[u], cx, floor_light0, mrgb);
+  }
+  rend_store4(pix, rgb_out, seg_out, nvalid);
+}
 
+#if MMR_LIT
+// ---- opt-in effects: cast shadows of the directional light, translucent bins
+enum { kFxShadows = 1, kFxTranslucent = 2 };  // MMX_RENDER_SHADOWS, MMX_RENDER_TRANSLUCENT (include/mmx_api.h)
+// The shadow map: per env, the height of the highest opaque, non-floor surface over each texel of a
+// kShN x kShN grid on the 2 m square centred on the scene's statistic centre (0, 0.3): 7.8 mm texels,
+// u16 heights (0 = nothing above the floor, else 1 + z in steps of 2^-14 m), 128 KB per env.  The
+// directional light shines along world -z, so a point is in shadow where the map is above it.
+static constexpr int kShN = 256;
+static constexpr float kShX0 = -1.f, kShY0 = -0.7f, kShScale = 128.f;  // texel = (p - origin) * scale
+static constexpr float kShZScale = 16384.f;
+static constexpr int kShBandRows = 128;  // map rows rasterised at a time (u32 per texel in LDS)
+// after the map, per env: the highest texel of every 8 x 8 block (kShC x kShC, same u16 code).  The lit
+// kernel keeps it in LDS (2 KB) and reads the map itself only where the block reaches above the point:
+// most pixels (table and floor away from the arm) are decided without a global load
+static constexpr int kShC = kShN / 8;
+static constexpr size_t kShStride = (size_t)kShN * kShN + kShC * kShC;  // u16 per env
+static constexpr int kMaxBin = 256;      // translucent triangles queued per band (the model has 180)
+__host__ DEV uint32_t rend_fbits(float v) {
+#ifdef __HIP_DEVICE_COMPILE__
+  unsigned b = __float_as_uint(v);
+  asm volatile("" : "+v"(b));  // opaque, as in rend_setup_abc: the range test below stays an integer test
+  return b;
+#else
+  uint32_t b;
+  __builtin_memcpy(&b, &v, 4);
+  return b;
+#endif
+}
+// texel index of the world point (x, y), or -1 outside the map.  The range test compares the bits:
+// a float lies in [0, kShN) exactly when its bits are below those of kShN (negative values, NaN and Inf
+// have larger bits), whatever the fp-math flags assume; the indices are clamped once more as integers.
+__host__ DEV int rend_shadow_texel(float x, float y) {
+  const float u = (x - kShX0) * kShScale, v = (y - kShY0) * kShScale;
+  const uint32_t lim = 0x43800000u;  // 256.0f
+  static_assert(kShN == 256, "lim holds the bits of (float)kShN");
+  if (rend_fbits(u) >= lim || rend_fbits(v) >= lim) return -1;
+  const int iu = min(max((int)u, 0), kShN - 1), iv = min(max((int)v, 0), kShN - 1);
+  return iv * kShN + iu;
+}
+// receiver test: the map above the point by more than the bias; outside the map = lit
+DEV bool rend_shadowed(const unsigned short* hm, const unsigned short* coarse, float x, float y, float z, float bias) {
+  const int k = rend_shadow_texel(x, y);
+  if (k < 0) return false;
+  const uint32_t hc = coarse[((k / kShN) >> 3) * kShC + ((k % kShN) >> 3)];
+  if (hc == 0u || !((float)(hc - 1u) * (1.f / kShZScale) > z + bias)) return false;
+  const uint32_t h = hm[k];
+  return h != 0u && (float)(h - 1u) * (1.f / kShZScale) > z + bias;
+}
+// light of the face of depth key `key` at its point on the pixel's ray dw (camera z = -1, so the point
+// at depth d is cx + d dw; the depth from the key's 20-bit scaled inverse depth, cell centre): the
+// face's light, without its directional term where the shadow map lies above the point
+DEV float rend_face_light(uint32_t key, V3 dw, V3 cx, float iz_lo, float iz_range, const unsigned short* hm,
+                          const unsigned short* coarse, const uint32_t* tm, const float* tl, const float* tsh, bool& dark) {
+  const int t = key & 4095;
+  const uint32_t m = tm[t];
+  dark = false;
+  if (hm && (m >> 8) != 0xFFFFu) {
+    const float q = ((float)(key >> 12) - 0.5f) * (1.f / 1048574.f);
+    const V3 p = cx + dw * (1.f / fmaf(q, iz_range, iz_lo));
+    dark = rend_shadowed(hm, coarse, p.x, p.y, p.z, (float)(m >> 8) * (1.f / 65536.f));
+  }
+  return dark ? tsh[t] : tl[t];
+}
+// shade_bg with the floor's shadow test and the colour as floats (for the blend); an unshadowed
+// pixel's packed value is shade_bg's, bit for bit (same expressions)
+DEV uint32_t shade_bg_lit(const V3& dw, const V3& cx, float floor_light0, float floor_light_sh, const float* mrgb,
+                          const unsigned short* hm, const unsigned short* coarse, float* rgb) {
+  const float s0 = -cx.z / dw.z;
+  const float fx = cx.x + s0 * dw.x, fy = cx.y + s0 * dw.y;
+  if (dw.z < 0.f && fabsf(fx) <= MMR_FLOOR_HALF && fabsf(fy) <= MMR_FLOOR_HALF) {
+    const float* mt = mrgb + 8 * MMR_FLOOR_MAT;
+    const float ddx = 0.5f - fx, ddy = 0.5f - fy;
+    const float l0 = hm && rend_shadowed(hm, coarse, fx, fy, 0.f, 0.003f) ? floor_light_sh : floor_light0;
+    const float light = fminf(l0 + 0.6f * rsqrtf(fmaf(ddx, ddx, fmaf(ddy, ddy, 2.25f))), 3.99f);
+    const bool alt = ((int)floorf(fx / mt[6]) + (int)floorf(fy / mt[6])) & 1;
+    const float* c = alt ? mt + 3 : mt;
+    rgb[0] = fminf(c[0] * light, 1.f); rgb[1] = fminf(c[1] * light, 1.f); rgb[2] = fminf(c[2] * light, 1.f);
+    return rend_pack(rgb[0], rgb[1], rgb[2], (uint32_t)mt[7]);
+  }
+  const float sky = 0.5f * (dw.z * rsqrtf(dot(dw, dw)) + 1.f);
+  rgb[0] = 0.3f * sky; rgb[1] = 0.5f * sky; rgb[2] = 0.7f * sky;
+  return rend_pack(rgb[0], rgb[1], rgb[2], 0u);
+}
+// depth key of a covered pixel the way the flat kernel forms it for this triangle: its column walk
+// (small boxes) and its tile walk (large boxes) round the interpolated depth differently, and the
+// nearest surface, hence the segment id, must not depend on the render mode
+DEV uint32_t rend_cover_as(const RTri& T, int t, bool small, int px, int py, float q0) {
+  const float x = px + 0.5f, y = py + 0.5f;
+  const float ex0 = rend_edge_x(T, 0, x), ex1 = rend_edge_x(T, 1, x), ex2 = rend_edge_x(T, 2, x);
+  const float e0 = fmaf(T.B[0], y, ex0), e1 = fmaf(T.B[1], y, ex1), e2 = fmaf(T.B[2], y, ex2);
+  if (fmaxf(e0, fmaxf(e1, e2)) > 0.f) return 0u;
+  if (!small) return rend_key(T, t, e0, e1, e2, q0);
+  const float qB = fmaf(T.B[0], T.w[0], fmaf(T.B[1], T.w[1], T.B[2] * T.w[2]));
+  const float qx = fmaf(ex0, T.w[0], fmaf(ex1, T.w[1], fmaf(ex2, T.w[2], q0)));
+  return rend_key_q(t, fmaf(qB, y, qx));
+}
+#endif  // MMR_LIT
+
+#if MMR_LIT
+// one workgroup per CU: the per-face light tables and the bins' queue and setups take the LDS past 80 KB
+extern "C" __global__ void __launch_bounds__(RWG) __attribute__((amdgpu_waves_per_eu(RWG / 256, RWG / 256)))
+mmx_render_lit_kernel(MMXState S, int env_base, const unsigned char* mask, int fx, const unsigned short* shmap) {
+#else
 extern "C" __global__ void __launch_bounds__(RWG) __attribute__((amdgpu_waves_per_eu(2 * RWG / 256, 2 * RWG / 256)))
 mmx_render_kernel(MMXState S, int env_base, const unsigned char* mask) {  // two workgroups per CU (LDS), registers to match
+#endif
   extern __shared__ __align__(16) unsigned char rsmem[];
   float4* vs = reinterpret_cast<float4*>(rsmem);                                 // [MMR_NVERT] screen
   float* bpose = reinterpret_cast<float*>(vs + MMR_NVERT);                        // [19][12]
@@ -279,6 +399,15 @@ mmx_render_kernel(MMXState S, int env_base, const unsigned char* mask) {  // two
   float* mrgb = reinterpret_cast<float*>(tinfo + MMR_NTRI);                       // [MMR_NMAT][8]
   unsigned short* smallq = reinterpret_cast<unsigned short*>(mrgb + 8 * MMR_NMAT); // [kBPW][MMR_NTRI]
   RTri* bigs = reinterpret_cast<RTri*>(smallq + kBPW * MMR_NTRI);                 // [kBigCache] setups
+#if MMR_LIT
+  float* tl = reinterpret_cast<float*>(bigs + kBigCache);                         // [MMR_NTRI] face light
+  float* tsh = tl + MMR_NTRI;                                                     // [MMR_NTRI] ... in shadow
+  uint32_t* tm = reinterpret_cast<uint32_t*>(tsh + MMR_NTRI);  // [MMR_NTRI] material | shadow bias (2^-16 m) << 8
+  RTri* binsT = reinterpret_cast<RTri*>(tm + MMR_NTRI);                           // [kMaxBin] setups of the band
+  unsigned short* binq = reinterpret_cast<unsigned short*>(binsT + kMaxBin);      // [kBPW][kMaxBin]
+  int* nbin = reinterpret_cast<int*>(binq + kBPW * kMaxBin);                      // [kBPW]
+  unsigned short* shc = reinterpret_cast<unsigned short*>(nbin + kBPW);           // [kShC][kShC] block maxima
+#endif
 
   const int tid = threadIdx.x;
   const int Sz = S.image_size;        // image side (projection, output)
@@ -308,6 +437,13 @@ mmx_render_kernel(MMXState S, int env_base, const unsigned char* mask) {  // two
     }
   }
   if (tid < kNbig) nbig[tid] = 0;
+#if MMR_LIT
+  if (tid < kBPW) nbin[tid] = 0;
+  const unsigned short* hm = (fx & kFxShadows) ? shmap + (size_t)i * kShStride : nullptr;
+  if (hm && tid < kShC * kShC / 2)
+    reinterpret_cast<uint32_t*>(shc)[tid] = reinterpret_cast<const uint32_t*>(hm + kShN * kShN)[tid];
+  static_assert(kShC * kShC / 2 <= RWG && kShStride % 2 == 0, "one dword of block maxima per lane, dword-aligned per env");
+#endif
   if (tid == 32) {
     const int c = ci == 0 ? MMX_CAM_OVERHEAD : MMX_CAM_WRIST;
     const M3 lq = qmat(Q4{MMX_cam_quat[4 * c], MMX_cam_quat[4 * c + 1], MMX_cam_quat[4 * c + 2], MMX_cam_quat[4 * c + 3]});
@@ -379,12 +515,35 @@ mmx_render_kernel(MMXState S, int env_base, const unsigned char* mask) {  // two
       const float lq = (float)(uint32_t)(fminf(light, 3.99f) * 16384.f) * (1.f / 16384.f);
       const float* mt = mrgb + 8 * MMR_tri_mat[t];
       tinfo[t] = rend_pack(fminf(mt[0] * lq, 1.f), fminf(mt[1] * lq, 1.f), fminf(mt[2] * lq, 1.f), (uint32_t)mt[7]);
+#if MMR_LIT
+      // the same face without the directional term, and the receiver's bias: 3 mm plus the height a
+      // map texel's half diagonal (5.5 mm) spans on the face's slope, at most 9 mm (faces turned away
+      // from the light have no directional term to lose: bias field 0xFFFF = never tested)
+      const float nzw = dot(n, l_top);
+      const float lsh = 0.3f + 0.6f * fmaxf(n.z, 0.f) + 0.4f * fmaxf(dot(n, normalize(lp_cam - pc)), 0.f);
+      tl[t] = lq;
+      tsh[t] = (float)(uint32_t)(fminf(lsh, 3.99f) * 16384.f) * (1.f / 16384.f);
+      const float slope = sqrtf(fmaxf(1.f - nzw * nzw, 0.f)) / fmaxf(nzw, 1e-3f);
+      const uint32_t bq = nzw > 0.f ? (uint32_t)(fminf(0.003f + 0.0055f * slope, 0.009f) * 65536.f) : 0xFFFFu;
+      tm[t] = (uint32_t)MMR_tri_mat[t] | (min(bq, 0xFFFFu) << 8);
+#endif
     }
     for (int kb = 0; kb < kBPW; kb++) {
       const int r0 = rowA + kb * rows;
       const int by0 = max(T.by0, r0), by1 = min(T.by1, r0 + rows - 1);
       if (by0 > by1) continue;
       const int area = (T.bx1 - T.bx0 + 1) * (by1 - by0 + 1);
+#if MMR_LIT
+      // translucent faces (the bins) wait in a queue of their own: the z-buffer then holds the nearest
+      // opaque surface, and the tile walk blends them over it (bit 15: the flat kernel's small path by
+      // box area; its large queue never fills at the sizes in use, so no overflow case is mirrored).
+      // kMaxBin holds every bin triangle of the model (tests/test_render_lit.py); one past it is dropped
+      if ((fx & kFxTranslucent) && MMR_mat_alpha[MMR_tri_mat[t]] < 1.f) {
+        const int kq = atomicAdd(nbin + kb, 1);
+        if (kq < kMaxBin) binq[kb * kMaxBin + kq] = (unsigned short)(t | (area > kSmallArea ? 0 : 0x8000));
+        continue;
+      }
+#endif
       int k = area > kSmallArea ? atomicAdd(nbig + 2 * kb, 1) : kMaxBig;
       if (k < kMaxBig) bigq[kb * kMaxBig + k] = (unsigned short)t;
       else if (area <= kTiny) smallq[kb * MMR_NTRI + atomicAdd(nbig + 2 * kb + 1, 1)] = (unsigned short)t;
@@ -395,7 +554,11 @@ mmx_render_kernel(MMXState S, int env_base, const unsigned char* mask) {  // two
   // the overhead camera is fixed: its background (floor / sky per pixel) is one table for every env
   // the per-sim background table holds a world-fixed camera's view: used only while the overhead
   // camera is attached to the world (a body-mounted one falls back to per-pixel shading)
+#if !MMR_LIT
   const uint32_t* bgtab = ci == 0 && MMX_cam_body[MMX_CAM_OVERHEAD] == 0 ? S.bg_overhead : nullptr;
+#else  // the floor receives shadows and lies under the bins: shaded per pixel (bit-identical to the table)
+  const float floor_light_sh = 0.3f + 0.6f * fmaxf(l_top.z, 0.f);
+#endif
   const int lane = tid & 63, lx = 4 * (lane & 3), ly = kTileRow(lane >> 2);
   unsigned char* img = S.images + ((size_t)i * 2 + ci) * Sz * Sz * 3;
   unsigned char* seg = S.seg + ((size_t)i * 2 + ci) * Sz * Sz;
@@ -412,6 +575,10 @@ mmx_render_kernel(MMXState S, int env_base, const unsigned char* mask) {  // two
   // the band's first kBigCache large triangles set up once for every wave's tile walk
   for (int q = tid; q < min((MMR_SKIP & 2) ? 0 : nbig[2 * kb], kBigCache); q += RWG)
     rend_setup(vs, bigq[kb * kMaxBig + q], Sz, row0, row1, iz_scale, bigs[q]);
+#if MMR_LIT
+  const int nbn = min(nbin[kb], kMaxBin);
+  for (int q = tid; q < nbn; q += RWG) rend_setup(vs, binq[kb * kMaxBin + q] & 4095, Sz, row0, row1, iz_scale, binsT[q]);
+#endif
   {  // small triangles: one per 8-lane group, walked column by column
     const int nsf = nbig[2 * kb + 1], ns = (MMR_SKIP & 1) ? 0 : nsf + nbig[8 + kb];
     // queue entry q: the tiny boxes [0, nsf) from the front, then the others from the back
@@ -541,6 +708,7 @@ mmx_render_kernel(MMXState S, int env_base, const unsigned char* mask) {  // two
         }
       }
     }
+#if !MMR_LIT
     for (int j = 0; j < kTPW; j++) {
       const int py = ty[j] + ly;
       if (tb + j >= ntiles || py >= row1) continue;
@@ -550,11 +718,94 @@ mmx_render_kernel(MMXState S, int env_base, const unsigned char* mask) {  // two
       shade4(best[j], tx[j] + lx, py, half, f, cR, cx, floor_light0, tinfo, mrgb, bgtab ? bgtab + (size_t)py * Sg : nullptr,
              reinterpret_cast<uint32_t*>(img + 3 * p0), reinterpret_cast<uint32_t*>(seg + p0), nvalid);
     }
+#else
+    // Lit shading of the batch's tiles.  Per pixel: the nearest opaque surface (or floor / sky) under
+    // its own light, its directional term dropped where the shadow map lies above its point; then the
+    // translucent faces in front of it, peeled back to front in registers: every pass walks the band's
+    // bin queue and takes, per pixel, the farthest key above the last one taken, blends it (0.4 over
+    // 0.6) under its own light and shadow test, and the wave leaves when a pass finds nothing in any
+    // lane.  A pixel no effect touches takes the flat kernel's packed value (tinfo / the background).
+#pragma unroll
+    for (int j = 0; j < kTPW; j++) {
+      const int py = ty[j] + ly;
+      // (wave-uniform: the peel's ballot needs every lane of the tile)
+      if (tb + j >= ntiles) continue;
+      const int nvalid = whole ? 4 : min(4, Sz - (tx[j] + lx));
+      const bool live = py < row1 && nvalid > 0;
+      V3 dw4[4];
+      rays4(tx[j] + lx, py, half, f, cR, dw4);
+      uint32_t pix[4], last[4];
+      float c[4][3];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const uint32_t key = best[j][u];
+        last[u] = key;
+        if (key != 0u) {
+          bool dark;
+          const float l = rend_face_light(key, dw4[u], cx, iz_lo, 1.f / iz_scale, hm, shc, tm, tl, tsh, dark);
+          const float* mt = mrgb + 8 * (tm[key & 4095] & 255u);
+          c[u][0] = fminf(mt[0] * l, 1.f); c[u][1] = fminf(mt[1] * l, 1.f); c[u][2] = fminf(mt[2] * l, 1.f);
+          pix[u] = dark ? rend_pack(c[u][0], c[u][1], c[u][2], (uint32_t)mt[7]) : tinfo[key & 4095];
+        } else {
+          pix[u] = shade_bg_lit(dw4[u], cx, floor_light0, floor_light_sh, mrgb, hm, shc, c[u]);
+        }
+      }
+      // the band's bin triangles whose box meets the tile, one lane per triangle, as ballot masks: the
+      // passes walk those only, and a tile no bin touches (most) is done
+      uint64_t bm[kMaxBin / 64];
+      bool anybin = false;
+#pragma unroll
+      for (int w = 0; w < kMaxBin / 64; w++) {
+        const int q = 64 * w + lane;
+        bool ok = false;
+        if (q < nbn) {
+          const RTri& Tq = binsT[q];
+          ok = !(Tq.bx1 < tx[j] || Tq.bx0 > tx[j] + 15 || Tq.by1 < ty[j] || Tq.by0 > ty[j] + 15);
+        }
+        bm[w] = __ballot(ok);
+        anybin |= bm[w] != 0;
+      }
+      if (anybin) {
+        for (;;) {
+          uint32_t cand[4] = {~0u, ~0u, ~0u, ~0u};
+#pragma unroll
+          for (int w = 0; w < kMaxBin / 64; w++)
+          for (uint64_t mq = bm[w]; mq; mq &= mq - 1) {
+            const int q = 64 * w + __builtin_ctzll(mq);
+            const int e = __builtin_amdgcn_readfirstlane((int)binq[kb * kMaxBin + q]);
+            const RTri T = binsT[q];  // uniform address: LDS broadcast
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+              const uint32_t key = rend_cover_as(T, e & 4095, (e & 0x8000) != 0, tx[j] + lx + u, py, q0);
+              if (key > last[u] && key < cand[u]) cand[u] = key;
+            }
+          }
+          const bool any = live && (cand[0] & cand[1] & cand[2] & cand[3]) != ~0u;
+          if (!__ballot(any)) break;
+#pragma unroll
+          for (int u = 0; u < 4; u++) {
+            if (cand[u] == ~0u) continue;
+            bool dark;
+            const float l = rend_face_light(cand[u], dw4[u], cx, iz_lo, 1.f / iz_scale, hm, shc, tm, tl, tsh, dark);
+            const float* mt = mrgb + 8 * (tm[cand[u] & 4095] & 255u);
+            for (int k = 0; k < 3; k++) c[u][k] = 0.4f * fminf(mt[k] * l, 1.f) + 0.6f * c[u][k];
+            last[u] = cand[u];
+            // the nearest layer so far names the segment
+            pix[u] = rend_pack(c[u][0], c[u][1], c[u][2], (uint32_t)mt[7]);
+          }
+        }
+      }
+      if (!live) continue;
+      const size_t p0 = (size_t)py * Sz + tx[j] + lx;  // image pixel of the lane's first pixel
+      rend_store4(pix, reinterpret_cast<uint32_t*>(img + 3 * p0), reinterpret_cast<uint32_t*>(seg + p0), nvalid);
+    }
+#endif
   }
   }  // bands
   RCLK(4);
   RCLK_END
 }
+#if !MMR_LIT
 #ifdef MMR_CLOCK
 extern "C" hipError_t mmx_render_clock(unsigned long long* out, int reset) {
   hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rclk), sizeof(unsigned long long) * 8);
@@ -608,10 +859,43 @@ extern "C" size_t mmx_render_lds_bytes() {
          sizeof(float) * 8 * MMR_NMAT + sizeof(unsigned short) * kBPW * MMR_NTRI + sizeof(RTri) * kBigCache;
 }
 
+// Opt-in render effects per sim (mmx_set_render_effects).  MMXState is the step kernels' argument too and
+// stays as it is, so the flags and the shadow map of a sim are kept here, under the sim's image buffer
+// (one per sim for its lifetime; the pose double buffering of camera rollouts copies the state but
+// shares it).  mmx_destroy unbinds.  No sim has asked for an effect: no lookup.
+extern "C" hipError_t mmx_launch_render_lit(const MMXState* S, int base, int count, const unsigned char* mask,
+                                            hipStream_t st, int flags, unsigned short* shmap);
+namespace {
+struct RendFx {
+  const unsigned char* images;
+  int flags;
+  unsigned short* shmap;
+};
+std::mutex g_fx_mu;
+std::vector<RendFx> g_fx;
+std::atomic<int> g_fx_n{0};
+}  // namespace
+extern "C" void mmx_render_effects_bind(const MMXState* S, int flags, unsigned short* shmap) {
+  std::lock_guard<std::mutex> lock(g_fx_mu);
+  for (size_t k = 0; k < g_fx.size(); k++)
+    if (g_fx[k].images == S->images) g_fx.erase(g_fx.begin() + k--);
+  if (flags) g_fx.push_back(RendFx{S->images, flags, shmap});
+  g_fx_n.store((int)g_fx.size(), std::memory_order_release);
+}
+
 // envs [base, base + count); with a device mask (N bytes) only the envs whose byte is set
 extern "C" hipError_t mmx_launch_render_masked(const MMXState* S, int base, int count, const unsigned char* mask,
                                                hipStream_t st) {
   if (count <= 0 || S->image_size <= 0) return hipSuccess;
+  if (g_fx_n.load(std::memory_order_acquire)) {
+    RendFx fx{nullptr, 0, nullptr};
+    {
+      std::lock_guard<std::mutex> lock(g_fx_mu);
+      for (const RendFx& e : g_fx)
+        if (e.images == S->images) fx = e;
+    }
+    if (fx.flags) return mmx_launch_render_lit(S, base, count, mask, st, fx.flags, fx.shmap);
+  }
   const int rows = rend_band_rows((S->image_size + 15) & ~15);
   const int bands = (S->image_size + rows - 1) / rows;
   hipLaunchKernelGGL(mmx_render_kernel, dim3((bands + kBPW - 1) / kBPW, 2, count), dim3(RWG), mmx_render_lds_bytes(), st, *S,
@@ -621,3 +905,188 @@ extern "C" hipError_t mmx_launch_render_masked(const MMXState* S, int base, int 
 extern "C" hipError_t mmx_launch_render(const MMXState* S, int base, int count, hipStream_t st) {
   return mmx_launch_render_masked(S, base, count, nullptr, st);
 }
+#else  // MMR_LIT
+
+// The shadow pass: one workgroup per env rasterises every opaque, non-floor triangle orthographically
+// from above (the directional light's view) into the env's height map, kShBandRows map rows at a time:
+// vertices to map coordinates (x, y in texels, the world height in the depth slot), triangles set up
+// one per lane with rend_setup_abc (both windings: a surface shadows whichever way it faces; its
+// integer-bit area cull drops NaN / Inf poses, its box is clipped to the band), small boxes walked by
+// their lane, larger ones by their wave, the largest queued for the whole workgroup, LDS atomicMax on
+// the quantised height per covered texel centre; the band is written out as packed u16, coalesced,
+// with the maxima of its 8 x 8 blocks.
+static constexpr int kShQ = 256;          // largest boxes queued per band (beyond it: walked by their wave)
+static constexpr int kShWaveArea = 2048;  // boxes up to this many texels: one wave
+static_assert(MMR_NTRI < 32768, "queue entry: triangle | winding << 15");
+// texels of T's box, first + k step (k = 0, 1, ...): the face's height where it covers the texel centre.
+// The box is clamped once more as integers: every index lies inside the band's buffer.
+DEV void shadow_walk(const RTri& T, uint32_t* hb, int row0, int row1, int first, int step) {
+  const int bx0 = max(T.bx0, 0), bx1 = min(T.bx1, kShN - 1), by0 = max(T.by0, row0), by1 = min(T.by1, row1 - 1);
+  const int w = bx1 - bx0 + 1, n = w * (by1 - by0 + 1);
+  if (w <= 0 || n <= 0) return;
+  for (int k = first; k < n; k += step) {
+    const int ry = k / w, px = bx0 + (k - ry * w), py = by0 + ry;
+    const float x = px + 0.5f, y = py + 0.5f;
+    const float e0 = rend_edge_at(T, 0, x, y), e1 = rend_edge_at(T, 1, x, y), e2 = rend_edge_at(T, 2, x, y);
+    if (fmaxf(e0, fmaxf(e1, e2)) > 0.f) continue;
+    const float z = fmaf(e0, T.w[0], fmaf(e1, T.w[1], e2 * T.w[2]));
+    atomicMax(hb + (py - row0) * kShN + px, (uint32_t)(min(max((int)(z * kShZScale), 0), 65534) + 1));
+  }
+}
+extern "C" __global__ void __launch_bounds__(RWG)
+mmx_shadow_kernel(MMXState S, int env_base, const unsigned char* mask, unsigned short* shmap) {
+  extern __shared__ __align__(16) unsigned char rsmem[];
+  float4* vs = reinterpret_cast<float4*>(rsmem);                 // [MMR_NVERT] map x, y, height
+  float* bpose = reinterpret_cast<float*>(vs + MMR_NVERT);        // [19][12]
+  uint32_t* hb = reinterpret_cast<uint32_t*>(bpose + 19 * 12);    // [kShBandRows][kShN]
+  unsigned short* bq = reinterpret_cast<unsigned short*>(hb + kShBandRows * kShN);  // [kShQ] large boxes of the band
+  int* nq = reinterpret_cast<int*>(bq + kShQ);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int i = env_base + blockIdx.x;
+  if (i >= S.N || (mask && !mask[i])) return;
+  const float* rp = S.rpose + (size_t)i * RNSLOT * 12;
+  if (tid < 19) {  // body poses, as in the render kernel
+    float* o = bpose + 12 * tid;
+    const int b = tid;
+    const int slot = b >= 1 && b <= 11 ? b - 1 : (b >= 16 ? b - 5 : -1);
+    if (slot >= 0) {
+      for (int k = 0; k < 12; k++) o[k] = rp[12 * slot + k];
+    } else {
+      const M3 R = qmat(Q4{MMX_body_quat[4 * b], MMX_body_quat[4 * b + 1], MMX_body_quat[4 * b + 2],
+                           MMX_body_quat[4 * b + 3]});
+      for (int k = 0; k < 9; k++) o[k] = b == 0 ? (k % 4 == 0 ? 1.f : 0.f) : R.m[k];
+      for (int k = 0; k < 3; k++) o[9 + k] = b == 0 ? 0.f : MMX_body_pos[3 * b + k];
+    }
+  }
+  __syncthreads();
+  for (int v = tid; v < MMR_NVERT; v += RWG) {
+    const float* o = bpose + 12 * MMR_vert_body[v];
+    M3 R;
+    for (int k = 0; k < 9; k++) R.m[k] = o[k];
+    const V3 w = V3{o[9], o[10], o[11]} + mul(R, V3{MMR_vert[3 * v], MMR_vert[3 * v + 1], MMR_vert[3 * v + 2]});
+    vs[v] = make_float4((w.x - kShX0) * kShScale, (w.y - kShY0) * kShScale, w.z, 1.f);
+  }
+  unsigned short* out = shmap + (size_t)i * kShStride;
+  for (int row0 = 0; row0 < kShN; row0 += kShBandRows) {
+    const int row1 = row0 + kShBandRows;
+    for (int k = tid; k < kShBandRows * kShN / 4; k += RWG) reinterpret_cast<uint4*>(hb)[k] = uint4{0u, 0u, 0u, 0u};
+    if (tid == 0) *nq = 0;
+    __syncthreads();  // (the first pass: the vertices too)
+    for (int t0 = (tid >> 6) * 64; t0 < MMR_NTRI; t0 += RWG) {  // (MMR_FLOOR_TRIS = 0: the floor is not in the tables)
+      const int t = t0 + lane;
+      RTri Ts;
+      bool ok = false;
+      int wind = 0;
+      if (t < MMR_NTRI && !(MMR_mat_alpha[MMR_tri_mat[t]] < 1.f)) {  // translucent faces cast no shadow
+        const int a = MMR_tri[3 * t], b = MMR_tri[3 * t + 1], c = MMR_tri[3 * t + 2];
+        ok = rend_setup_abc(vs, a, b, c, kShN, row0, row1, 1.f, Ts);
+        if (!ok) {
+          ok = rend_setup_abc(vs, a, c, b, kShN, row0, row1, 1.f, Ts);
+          wind = 1;
+        }
+      }
+      // by box size: up to 16 texels (most of the robot's faces) the face's own lane walks it; the
+      // largest (the table's faces) wait for the whole workgroup; the rest are walked by the wave
+      const int area = ok ? (Ts.bx1 - Ts.bx0 + 1) * (Ts.by1 - Ts.by0 + 1) : 0;
+      if (ok && area > kShWaveArea) {
+        const int k = atomicAdd(nq, 1);
+        if (k < kShQ) {
+          bq[k] = (unsigned short)(t | (wind << 15));
+          ok = false;
+        }
+      }
+      if (ok && area <= 16) {
+        shadow_walk(Ts, hb, row0, row1, 0, 1);
+        ok = false;
+      }
+      for (uint64_t live = __ballot(ok); live; live &= live - 1) {
+        const int src = __builtin_ctzll(live);
+        RTri T;
+#pragma unroll
+        for (int e = 0; e < 3; e++) {
+          T.A[e] = __shfl(Ts.A[e], src);
+          T.B[e] = __shfl(Ts.B[e], src);
+          T.C[e] = __shfl(Ts.C[e], src);
+          T.w[e] = __shfl(Ts.w[e], src);
+        }
+        T.bx0 = __shfl(Ts.bx0, src);
+        T.bx1 = __shfl(Ts.bx1, src);
+        T.by0 = __shfl(Ts.by0, src);
+        T.by1 = __shfl(Ts.by1, src);
+        shadow_walk(T, hb, row0, row1, lane, 64);
+      }
+    }
+    __syncthreads();
+    for (int q = 0; q < min(*nq, kShQ); q++) {  // uniform: every wave sets the triangle up, the lanes share its box
+      const int e = bq[q], t = e & 0x7FFF;
+      const int a = MMR_tri[3 * t], b = MMR_tri[3 * t + 1], c = MMR_tri[3 * t + 2];
+      RTri T;
+      if (!rend_setup_abc(vs, a, (e >> 15) ? c : b, (e >> 15) ? b : c, kShN, row0, row1, 1.f, T)) continue;
+      shadow_walk(T, hb, row0, row1, tid, RWG);
+    }
+    __syncthreads();
+    uint2* o64 = reinterpret_cast<uint2*>(out + (size_t)row0 * kShN);
+    for (int k = tid; k < kShBandRows * kShN / 4; k += RWG) {
+      const uint4 h = reinterpret_cast<const uint4*>(hb)[k];
+      o64[k] = uint2{h.x | (h.y << 16), h.z | (h.w << 16)};
+    }
+    // the band's 8 x 8 block maxima: one block per lane
+    static_assert((kShBandRows / 8) * kShC <= RWG, "a band's blocks: one per lane");
+    if (tid < (kShBandRows / 8) * kShC) {
+      const int by = tid / kShC, bx = tid % kShC;
+      uint32_t mx = 0u;
+      for (int r = 0; r < 8; r++)
+        for (int c = 0; c < 8; c++) mx = max(mx, hb[(8 * by + r) * kShN + 8 * bx + ((c + tid) & 7)]);
+      out[kShN * kShN + (row0 / 8 + by) * kShC + bx] = (unsigned short)mx;
+    }
+    __syncthreads();
+  }
+}
+
+extern "C" int mmx_render_shadow_texel(float x, float y) { return rend_shadow_texel(x, y); }
+extern "C" int mmx_render_shadow_map_side() { return kShN; }
+
+static size_t lit_lds_bytes() {
+  return sizeof(float4) * MMR_NVERT + sizeof(float) * 19 * 12 + sizeof(uint32_t) * kZbWords +
+         sizeof(unsigned short) * kBPW * kMaxBig + kNbig * sizeof(int) + 12 * sizeof(float) + sizeof(uint32_t) * MMR_NTRI +
+         sizeof(float) * 8 * MMR_NMAT + sizeof(unsigned short) * kBPW * MMR_NTRI + sizeof(RTri) * kBigCache +
+         3 * sizeof(float) * MMR_NTRI + sizeof(RTri) * kMaxBin + sizeof(unsigned short) * kBPW * kMaxBin + sizeof(int) * kBPW +
+         sizeof(unsigned short) * kShC * kShC;
+}
+static size_t shadow_lds_bytes() {
+  return sizeof(float4) * MMR_NVERT + sizeof(float) * 19 * 12 + sizeof(uint32_t) * kShBandRows * kShN +
+         sizeof(unsigned short) * kShQ + sizeof(int);
+}
+static_assert(sizeof(float4) * MMR_NVERT + sizeof(float) * 19 * 12 + sizeof(uint32_t) * kShBandRows * kShN +
+                      sizeof(unsigned short) * kShQ + sizeof(int) <= 160 * 1024,
+              "shadow pass: one band of the map beside the vertices in a CU's LDS");
+static_assert(kShN % kShBandRows == 0 && (kShBandRows * kShN) % 4 == 0, "whole bands, whole groups of 4 texels");
+
+// the render of envs [base, base + count) with effects: the shadow pass (when asked for) on the same
+// stream, pose buffer and env mask, then the lit kernel
+extern "C" hipError_t mmx_launch_render_lit(const MMXState* S, int base, int count, const unsigned char* mask,
+                                            hipStream_t st, int flags, unsigned short* shmap) {
+  if (count <= 0 || S->image_size <= 0) return hipSuccess;
+  if ((flags & kFxShadows) && !shmap) return hipErrorInvalidValue;
+  static const hipError_t attr = [] {  // dynamic LDS past the default limit, once
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mmx_render_lit_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lit_lds_bytes());
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(mmx_shadow_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)shadow_lds_bytes());
+    return e;
+  }();
+  if (attr != hipSuccess) return attr;
+  if (flags & kFxShadows) {
+    hipLaunchKernelGGL(mmx_shadow_kernel, dim3(count), dim3(RWG), shadow_lds_bytes(), st, *S, base, mask, shmap);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  const int rows = rend_band_rows((S->image_size + 15) & ~15);
+  const int bands = (S->image_size + rows - 1) / rows;
+  hipLaunchKernelGGL(mmx_render_lit_kernel, dim3((bands + kBPW - 1) / kBPW, 2, count), dim3(RWG), lit_lds_bytes(), st, *S,
+                     base, mask, flags, shmap);
+  return hipGetLastError();
+}
+extern "C" size_t mmx_render_shadow_map_bytes() { return sizeof(unsigned short) * kShStride; }
+#endif  // MMR_LIT

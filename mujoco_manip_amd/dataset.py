@@ -405,7 +405,8 @@ def _merge_image_stats(fs: np.ndarray, npx: int) -> dict:
 
 def collect_episodes(num_episodes: int, task_list, feature_keys, *, reward_type="staged", randomize_objects=False,
                      seed=0, spawn_x_range=(-0.20, 0.20), spawn_y_range=(0.30, 0.45), num_envs=1024, device=0,
-                     max_gym_steps=5000, on_step=None, sink=None, image_size=IMAGE_SIZE, episode_ids=None):
+                     max_gym_steps=5000, on_step=None, sink=None, image_size=IMAGE_SIZE, episode_ids=None,
+                     render_effects=()):
     """Run `num_episodes` reference run_episode loops (generate_dataset.py:83-198) side by side,
     or, with `episode_ids`, only those episodes of the `num_episodes`-episode job (a rank's shard,
     rank_episodes): each keeps its global index, seed and task.
@@ -440,7 +441,8 @@ def collect_episodes(num_episodes: int, task_list, feature_keys, *, reward_type=
     env = PickPlaceVecEnv(N, tasks=[tuple(t) for t in task_list], action_mode="abs_pos", reward_type=reward_type,
                           randomize_objects=randomize_objects, spawn_x_range=tuple(spawn_x_range),
                           spawn_y_range=tuple(spawn_y_range), autoreset=False, device=device,
-                          image_size=image_size if use_images else 0)
+                          image_size=image_size if use_images else 0,
+                          render_effects=tuple(render_effects) if use_images else ())
     dev = env.device
     need_actions = bool(set(feature_keys) & set(ACTION_KEYS))
     need_reward = "next.reward" in feature_keys and reward_type == "staged"
@@ -1097,7 +1099,8 @@ def _features_at(feats: dict, image_size: int) -> dict:
 
 def generate(repo_id, num_episodes=100, root="./datasets", task=None, tasks="all", reward_type="staged",
              randomize_objects=False, seed=0, spawn_x_range=(-0.20, 0.20), spawn_y_range=(0.30, 0.45),
-             features=None, num_envs=1024, device=0, image_size=IMAGE_SIZE, rank=0, world_size=1):
+             features=None, num_envs=1024, device=0, image_size=IMAGE_SIZE, rank=0, world_size=1,
+             render_effects=()):
     """generate_dataset.main (generate_dataset.py:201-333) with the episodes batched on the GPU and
     streamed to the LeRobot writer as they finish.
 
@@ -1105,7 +1108,13 @@ def generate(repo_id, num_episodes=100, root="./datasets", task=None, tasks="all
     e = r (mod world_size) with their global seeds and tasks and writes them as a LeRobot dataset
     of its own in `<root>/<repo_id>/shard-RRR-of-WWW` (local episode indices 0..n-1, the global
     ones in its metadata.json under "shard"); merge_shards then writes the dataset a single
-    process would have written.  Returns (path written, info)."""
+    process would have written.  render_effects: the opt-in camera effects of the frames
+    ("shadows", "translucent_bins"; PickPlaceVecEnv), recorded in the stored config when not empty.
+    Returns (path written, info)."""
+    from ._lib import render_effect_flags
+
+    render_effects = tuple(render_effects or ())
+    render_effect_flags(render_effects)  # names checked before anything is written
     if not repo_id:
         raise ValueError("repo_id is required (e.g. repo_id=user/pick-place)")
     task_list = resolve_tasks(task, tasks)
@@ -1124,7 +1133,7 @@ def generate(repo_id, num_episodes=100, root="./datasets", task=None, tasks="all
     _, seeds = collect_episodes(num_episodes, task_list, set(feats), reward_type=reward_type,
                                 randomize_objects=randomize_objects, seed=seed, spawn_x_range=spawn_x_range,
                                 spawn_y_range=spawn_y_range, num_envs=num_envs, device=device, sink=sink,
-                                image_size=image_size, episode_ids=ids)
+                                image_size=image_size, episode_ids=ids, render_effects=render_effects)
     cfg = {"repo_id": repo_id, "num_episodes": int(num_episodes), "root": root,
            "task": list(task) if task is not None else None, "tasks": tasks, "reward_type": reward_type,
            "randomize_objects": bool(randomize_objects), "seed": int(seed), "spawn_x_range": list(spawn_x_range),
@@ -1132,6 +1141,8 @@ def generate(repo_id, num_episodes=100, root="./datasets", task=None, tasks="all
            "features": list(features) if features is not None else None}
     if image_size != IMAGE_SIZE:
         cfg["image_size"] = int(image_size)
+    if render_effects:
+        cfg["render_effects"] = list(render_effects)
     if seeds is not None:
         cfg["episode_seeds"] = [int(s) for s in seeds]
     md = cfg if world_size == 1 else dict(cfg, shard={"rank": int(rank), "world_size": int(world_size),
@@ -1226,6 +1237,8 @@ def main(argv=None):
     ap.add_argument("--features", nargs="*", default=None)
     ap.add_argument("--num-envs", type=int, default=1024, help="parallel envs per GPU")
     ap.add_argument("--image-size", type=int, default=IMAGE_SIZE)
+    ap.add_argument("--render-effects", nargs="*", default=(), choices=("shadows", "translucent_bins"),
+                    help="opt-in camera effects: cast shadows, translucent bins (default: neither)")
     ap.add_argument("--no-merge", action="store_true", help="sharded run: keep the per-rank shards only")
     ap.add_argument("--dist-backend", default=None, help="sharded run: collective backend (default nccl = RCCL)")
     a = ap.parse_args(argv)
@@ -1237,7 +1250,7 @@ def main(argv=None):
     t0 = time.perf_counter()
     path, info = generate(a.repo_id, a.num_episodes, a.root, a.task, a.tasks, a.reward_type, a.randomize_objects,
                           a.seed, a.spawn_x_range, a.spawn_y_range, a.features, a.num_envs, device=local_rank,
-                          image_size=a.image_size, rank=rank, world_size=world)
+                          image_size=a.image_size, rank=rank, world_size=world, render_effects=tuple(a.render_effects))
     summary = [float(info["total_episodes"]), float(info["total_frames"]), time.perf_counter() - t0]
     if world > 1:
         import torch

@@ -146,7 +146,7 @@ class PickPlaceGymEnv(_Base):
                  action_mode: str = "ee_pos_quat_g_rel", reward_type: str = "dense", image_size: int = IMAGE_SIZE,
                  render_mode: str = "rgb_array", max_episode_steps: int = MAX_EPISODE_STEPS,
                  randomize_objects: bool = False, spawn_x_range=(-0.20, 0.20), spawn_y_range=(0.30, 0.45),
-                 device: int = 0):
+                 device: int = 0, render_effects=()):
         if action_mode not in ACTION_MODES:
             raise ValueError(f"action_mode must be one of {ACTION_MODES}, got '{action_mode}'")
         # xml_path is accepted for signature compatibility: the model is compiled offline
@@ -155,7 +155,8 @@ class PickPlaceGymEnv(_Base):
         self._vec = PickPlaceVecEnv(1, task=task, tasks=tasks, action_mode=action_mode, reward_type=reward_type,
                                     image_size=image_size, render_mode=render_mode,
                                     max_episode_steps=max_episode_steps, randomize_objects=randomize_objects,
-                                    spawn_x_range=spawn_x_range, spawn_y_range=spawn_y_range, device=device)
+                                    spawn_x_range=spawn_x_range, spawn_y_range=spawn_y_range, device=device,
+                                    render_effects=render_effects)
         self._action_mode = action_mode
         self._reward_type = reward_type
         self._image_size = image_size

@@ -6,8 +6,10 @@ types.  Differences, all documented in DESIGN.md:
   * observations are torch tensors on the GPU ([N, ...]); with image_size > 0 the
     `image_overhead` / `image_wrist` keys are uint8 [N, S, S, 3] from the batched HIP rasteriser
     (mmx_render.hip: the Panda's visual parts reduced to convex pieces and clustered meshes per
-    part, flat-lit with the scene's lights, no shadows or specular), image_size = 0
-    skips them;
+    part, flat-lit with the scene's lights, no specular), image_size = 0 skips them.
+    By default nothing casts a shadow and the bins are opaque; render_effects=("shadows",
+    "translucent_bins") (either or both) turns on the directional light's cast shadows and the
+    bins' alpha 0.4, as the reference's mujoco.Renderer draws them (segment ids are the same);
   * reset(seed=s) seeds env i with s + i (gymnasium vector convention); a list gives one
     seed per env;
   * with autoreset=True an env that terminated/truncated (or whose FSM expert finished: reported
@@ -31,7 +33,7 @@ class PickPlaceVecEnv:
                  render_mode: str | None = None, max_episode_steps: int = MAX_EPISODE_STEPS,
                  randomize_objects: bool = False, spawn_x_range=(-0.20, 0.20), spawn_y_range=(0.30, 0.45),
                  autoreset: bool = False, device: int = 0, solver_iterations: int = 30,
-                 solver_tolerance: float = 1e-6):
+                 solver_tolerance: float = 1e-6, render_effects=()):
         if not torch.cuda.is_available():
             raise RuntimeError("PickPlaceVecEnv needs an MI355X GPU (HIP); no CPU fallback exists")
         pool = TASK_SETS[tasks] if isinstance(tasks, str) else list(tasks)
@@ -50,7 +52,8 @@ class PickPlaceVecEnv:
                             task_pool=[task_index(t) for t in pool],
                             fixed_task=None if task is None else task_index(task), image_size=image_size,
                             autoreset=autoreset, solver_iterations=solver_iterations,
-                            solver_tolerance=solver_tolerance, device=device, stream=stream)
+                            solver_tolerance=solver_tolerance, device=device, stream=stream,
+                            render_effects=render_effects)
         s = self.sim
         self.action_dim = s.action_dim
         self._obs = s.view("obs", _lib.NOBS)

@@ -188,14 +188,15 @@ def build(robot_tris=ROBOT_TRIS, hand_weight=HAND_WEIGHT):
     # checker floor colours (pick_and_place_scene.xml:19-22)
     tex = {t.get("name"): t for t in scene.find("asset").iter("texture")}["groundplane"]
     materials = [dict(name="groundplane", rgb=rgba(tex.get("rgb1")), rgb2=rgba(tex.get("rgb2")), checker=0.1,
-                      seg=SEG["floor"])]
+                      seg=SEG["floor"], alpha=1.0)]
     mat_index = {}
 
     def material(name, seg):
         key = (name, seg)
         if key not in mat_index:
             mat_index[key] = len(materials)
-            materials.append(dict(name=name, rgb=mats[name][:3], rgb2=mats[name][:3], checker=0.0, seg=seg))
+            materials.append(dict(name=name, rgb=mats[name][:3], rgb2=mats[name][:3], checker=0.0, seg=seg,
+                                  alpha=mats[name][3]))
         return mat_index[key]
 
     parts = []  # (body id, verts [k,3] body frame, faces, material index)
@@ -305,6 +306,8 @@ def emit(rm, path):
     L.append(CM.c_array("MMR_mat_rgb", "float", [m["rgb"] + m["rgb2"] for m in rm["materials"]], "{:.9g}"))
     L.append(CM.c_array("MMR_mat_checker", "float", [m["checker"] for m in rm["materials"]], "{:.9g}"))
     L.append(CM.c_array("MMR_mat_seg", "unsigned char", [m["seg"] for m in rm["materials"]], "{}"))
+    # opacity (rgba's alpha): < 1 = drawn translucent and casting no shadow under the opt-in render effects
+    L.append(CM.c_array("MMR_mat_alpha", "float", [m["alpha"] for m in rm["materials"]], "{:.9g}"))
     L.append("\n#endif /* MMX_RENDER_GEN_H */\n")
     with open(path, "w") as f:
         f.write("".join(L).replace(CM.QUAL + " ", "MMR_QUAL "))

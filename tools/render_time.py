@@ -1,7 +1,7 @@
 """Render-only timing (experiment infrastructure): mmx_forward over C5-shaped states with and
 without cameras; the difference is the render kernel's time for all envs and both cameras.
 
-  python tools/render_time.py [--envs 8192] [--size 128] [--reps 20]
+  python tools/render_time.py [--envs 8192] [--size 128] [--reps 20] [--render-effects shadows translucent_bins]
 """
 import argparse
 import json
@@ -31,12 +31,14 @@ def main():
     ap.add_argument("--envs", type=int, default=8192)
     ap.add_argument("--size", type=int, default=128)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--render-effects", nargs="*", default=(), help="opt-in camera effects (default: the flat images)")
     a = ap.parse_args()
-    res = {"envs": a.envs, "image_size": a.size, "lib": os.environ.get("MMX_LIB_PATH", "libmmx.so"), "points": []}
+    res = {"envs": a.envs, "image_size": a.size, "render_effects": list(a.render_effects), "lib": os.environ.get("MMX_LIB_PATH", "libmmx.so"), "points": []}
     envs = {}
     for size in (a.size, 0):
         envs[size] = PickPlaceVecEnv(a.envs, tasks="all", action_mode="abs_pos", reward_type="staged",
-                                     randomize_objects=True, autoreset=True, image_size=size)
+                                     randomize_objects=True, autoreset=True, image_size=size,
+                                     render_effects=tuple(a.render_effects) if size else ())
         envs[size].reset(seed=[_lib.episode_seed(42, i) for i in range(a.envs)])
     for chunk in range(4):  # states spread over the episode (approach, grasp, transport, release)
         for e in envs.values():
