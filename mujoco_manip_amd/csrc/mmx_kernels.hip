@@ -2160,9 +2160,9 @@ DEV float chol_solve_arrow(EnvSh& E, const float* hrow, float v, int cpl) {
 }
 
 // H^{-1} v: the block form unless two cubes are coupled (a cube resting on or pushing another).
-// The general solve stays inline although C3 never runs it: out of line (its Hessian row passed by
-// value, no register save on either side) the kernel is ~3,100 instructions shorter but no faster
-// (-0.01 % on the medians, the spread 0.3 %: profiles/r07_ab_nocsr.json).
+// The general solve stays inline although no C3 episode reaches it (tests/test_cube_contact_kat.py
+// does): out of line (its Hessian row by value, no register save on either side) the kernel is ~3,100
+// instructions shorter but no faster (-0.01 % on the medians, the spread 0.3 %: profiles/r07_ab_nocsr.json).
 DEV float chol_solve(EnvSh& E, const float* hrow, float v, int cpl) {
   float* stats = E.stats;
   CLK_DECL;

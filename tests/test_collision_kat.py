@@ -100,45 +100,46 @@ def ordered(m, ga, gb, n_ab):
 
 
 # --------------------------------------------------------------------------- scenes
-def scene_cube_on_cube(m):
-    """Green cube on the red one, shifted by half an edge in x and 5 mm in y, 1 mm deep: a face
-    contact whose polygon is the overlap rectangle x in [x0, x0 + h], y in [y0 - h + 5 mm, y0 + h],
-    4 corners at depth 1 mm, midway between the faces (z = top - 0.5 mm)."""
+def scene_cube_on_cube(m, lo=0, up=1):
+    """Green cube on the red one (or cube `up` on cube `lo`: the three cube-on-cube scenes take
+    the pair), shifted by half an edge in x and 5 mm in y, 1 mm deep: a face contact whose polygon
+    is the overlap rectangle x in [x0, x0 + h], y in [y0 - h + 5 mm, y0 + h], 4 corners at depth
+    1 mm, midway between the faces (z = top - 0.5 mm)."""
     q = parked(m)
     x0, y0, z0, d = 0.6, -0.2, 0.8, 0.001
-    put_cube(q, 0, [x0, y0, z0])
-    put_cube(q, 1, [x0 + H, y0 + 0.005, z0 + 2 * H - d])
+    put_cube(q, lo, [x0, y0, z0])
+    put_cube(q, up, [x0 + H, y0 + 0.005, z0 + 2 * H - d])
     top = z0 + H
     pts = [[x, y, top - d / 2] for x in (x0, x0 + H) for y in (y0 - H + 0.005, y0 + H)]
-    a, b = m.find("obj_red", "box"), m.find("obj_green", "box")
+    a, b = m.find(CUBES[lo], "box"), m.find(CUBES[up], "box")
     return q, [dict(pair=ordered(m, a, b, [0, 0, 1]), depth=d, pts=pts)]
 
 
-def scene_cube_on_cube_turned(m):
+def scene_cube_on_cube_turned(m, lo=0, up=1):
     """Green cube centred on the red one, turned 45 deg about z, 0.7 mm deep: the overlap of the
     two squares is a regular octagon (the turned square's edges |x| + |y| = h sqrt 2 cut the
     lower one's |x| = h, |y| = h at (sqrt 2 - 1) h): 8 contacts at its corners."""
     q = parked(m)
     x0, y0, z0, d = -0.6, -0.3, 0.9, 0.0007
-    put_cube(q, 0, [x0, y0, z0])
-    put_cube(q, 1, [x0, y0, z0 + 2 * H - d], axis_rot([0, 0, 1], np.pi / 4))
+    put_cube(q, lo, [x0, y0, z0])
+    put_cube(q, up, [x0, y0, z0 + 2 * H - d], axis_rot([0, 0, 1], np.pi / 4))
     s = (np.sqrt(2) - 1) * H
     pts = [[x0 + a, y0 + b, z0 + H - d / 2] for a, b in ((H, s), (H, -s), (-H, s), (-H, -s), (s, H), (-s, H),
                                                          (s, -H), (-s, -H))]
-    return q, [dict(pair=ordered(m, m.find("obj_red", "box"), m.find("obj_green", "box"), [0, 0, 1]), depth=d,
+    return q, [dict(pair=ordered(m, m.find(CUBES[lo], "box"), m.find(CUBES[up], "box"), [0, 0, 1]), depth=d,
                     pts=pts)]
 
 
-def scene_cube_edge_on_edge(m):
+def scene_cube_edge_on_edge(m, lo=0, up=1):
     """Red cube turned 45 deg about x (top edge along x), green cube above it turned 45 deg about
     y (bottom edge along y), the edges crossing 0.9 mm deep: the edge-edge axis (z) is the
     separating-axis minimum, one contact at the midpoint of the edges' closest points."""
     q = parked(m)
     x0, y0, z0, d = 0.5, 0.9, 0.7, 0.0009
     r2 = H * np.sqrt(2)
-    put_cube(q, 0, [x0, y0, z0], axis_rot([1, 0, 0], np.pi / 4))
-    put_cube(q, 1, [x0, y0, z0 + 2 * r2 - d], axis_rot([0, 1, 0], np.pi / 4))
-    return q, [dict(pair=ordered(m, m.find("obj_red", "box"), m.find("obj_green", "box"), [0, 0, 1]), depth=d,
+    put_cube(q, lo, [x0, y0, z0], axis_rot([1, 0, 0], np.pi / 4))
+    put_cube(q, up, [x0, y0, z0 + 2 * r2 - d], axis_rot([0, 1, 0], np.pi / 4))
+    return q, [dict(pair=ordered(m, m.find(CUBES[lo], "box"), m.find(CUBES[up], "box"), [0, 0, 1]), depth=d,
                     pts=[[x0, y0, z0 + r2 - d / 2]])]
 
 
@@ -364,6 +365,22 @@ def test_oracle_box_scenes(raw, idx):
     assert not extra, extra
 
 
+CUBE_SCENES = [scene_cube_on_cube, scene_cube_on_cube_turned, scene_cube_edge_on_edge]
+CUBE_PAIRS = [(0, 2), (1, 2)]  # (red, blue), (green, blue); BOX_SCENES run (red, green)
+
+
+@pytest.mark.parametrize("lo,up", CUBE_PAIRS)
+def test_oracle_cube_pair_scenes(raw, lo, up):
+    """The three cube-on-cube scenes with the other two cube pairs."""
+    ids = compiled_ids(raw)
+    for f in CUBE_SCENES:
+        q, wants = f(raw, lo, up)
+        con = oracle_contacts(q)
+        for w in wants:
+            check(raw, ids, con, w, CPU_TOL, f"{f.__name__}({lo}, {up})")
+        assert {(c[0], c[1]) for c in con} == {(ids[w["pair"][0]], ids[w["pair"][1]]) for w in wants}
+
+
 def test_oracle_mesh_scenes(raw):
     ids = compiled_ids(raw)
     for s, q in mesh_scenes(raw):
@@ -407,6 +424,18 @@ def test_gpu_box_scenes(raw):
     for (q, wants), con, f in zip(scenes, got, BOX_SCENES):
         for w in wants:
             check(raw, ids, con, w, GPU_TOL_CONVEX if w.get("convex") else GPU_TOL_BOX, f.__name__)
+
+
+@pytest.mark.gpu
+def test_gpu_cube_pair_scenes(raw):
+    """The cube-on-cube scenes with the pairs (red, blue) and (green, blue): the box-box narrowphase
+    and the pair order do not depend on which two cubes touch."""
+    ids = compiled_ids(raw)
+    scenes = [(f, lo, up, f(raw, lo, up)) for lo, up in CUBE_PAIRS for f in CUBE_SCENES]
+    got, _ = gpu_contacts([q for _, _, _, (q, _) in scenes])
+    for (f, lo, up, (q, wants)), con in zip(scenes, got):
+        for w in wants:
+            check(raw, ids, con, w, GPU_TOL_BOX, f"{f.__name__}({lo}, {up})")
 
 
 @pytest.mark.gpu

@@ -63,12 +63,14 @@ def a_hat_pyramid(tran=TRAN, mu0=MU[0], impratio=1.0):
     return 2.0 * mu0 * mu0 * (tran + mu0 * mu0 * tran) / impratio
 
 
-def rest_penetration(ncon, a_hat=None, edges=6):
-    """Penetration r < 0 at which `ncon` equal corner contacts of a resting cube carry its weight:
-    with v = 0 and qacc = 0 every edge is active and pushes D aref = k d(r)^2 |r| / ((1 - d) A_hat)
-    along the normal, so ncon * edges * that = m g.  Solved by bisection (monotone in |r|)."""
+def rest_penetration(ncon, a_hat=None, edges=6, load=M_CUBE * G, tran=TRAN):
+    """Penetration r < 0 at which `ncon` equal contacts carry `load` (by default a resting cube's
+    weight on its corner contacts): with v = 0 and qacc = 0 every edge is active and pushes
+    D aref = k d(r)^2 |r| / ((1 - d) A_hat) along the normal, so ncon * edges * that = load.  `tran`
+    is the sum of the two bodies' translational invweight0 in A_hat (20 for a cube on the static
+    table, 20 + 20 for a cube on a cube).  Solved by bisection (monotone in |r|)."""
     K, _ = kb()
-    A = a_hat_pyramid() if a_hat is None else a_hat
+    A = a_hat_pyramid(tran) if a_hat is None else a_hat
 
     def total(p):
         d = impedance(p)
@@ -77,7 +79,7 @@ def rest_penetration(ncon, a_hat=None, edges=6):
     lo, hi = 0.0, 0.01
     for _ in range(200):
         mid = 0.5 * (lo + hi)
-        if total(mid) < M_CUBE * G:
+        if total(mid) < load:
             lo = mid
         else:
             hi = mid
