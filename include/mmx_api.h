@@ -143,6 +143,39 @@ int mmx_expert_plan(mmx_sim* sim, int32_t n_steps, float* action_dev_out);
  * Requires action_mode == MMX_ACTION_ABS_POS. */
 int mmx_rollout_expert(mmx_sim* sim, int32_t n_env_steps);
 
+/* Per-step record of a rollout: caller-owned device arrays [T][N][F] (T = n_env_steps), NULL = not
+ * recorded.  Slice k holds what the sim-owned buffer of the same name (mmx_buffers) holds after env
+ * step k of the rollout. */
+typedef struct {
+  float* obs;                /* [T][N][85] */
+  float* reward;             /* [T][N] */
+  int32_t* done;             /* [T][N][3] terminated, truncated, success */
+  float* reward_components;  /* [T][N][6] */
+  float* target;             /* [T][N][4] decoded EE target + gripper value (the expert's abs_pos action) */
+  int32_t* episode_i;        /* [T][N][18] */
+  float* qpos;               /* [T][N][30] */
+  float* qvel;               /* [T][N][27] */
+} mmx_trajectory;
+
+/* Action-sequence rollouts (the driver loops of scripts/replay_actions.py:128-148 and
+ * scripts/generate_dataset.py:140-196) in fused launches, with an optional per-step record.
+ * mmx_rollout_actions steps every env through actions_dev, a device array [T][N][action_dim] fp32:
+ * afterwards every sim-owned buffer is bit for bit what T calls mmx_step(actions_dev + k * N *
+ * action_dim, action_dim), k = 0 .. T - 1, leave, and slice k of every array of rec is bit for bit what
+ * the matching sim-owned buffer holds after the k-th of those calls.  mmx_rollout_expert_record is the
+ * same against T x (mmx_expert_plan(16) -> mmx_step): mmx_rollout_expert with a record; rec->target is
+ * then the expert's action.  Autoreset, truncation, divergence resets and MMX_ESAMPLING (reported by the
+ * next mmx_synchronize) behave as in those loops; on the step an env autoresets the record holds, like
+ * the buffers, the first observation of the new episode (the ended episode's final observation is not
+ * kept).  With cameras the images / seg buffers hold the last step's frame; images are not recorded.
+ * rec may be NULL (nothing recorded); the arrays must stay valid until the sim's stream has run the
+ * rollout.  n_env_steps == 0 does nothing and returns MMX_OK.  MMX_EINVAL, with nothing launched, for a
+ * NULL sim, NULL actions_dev, n_env_steps < 0, action_dim below the action mode's dimension, and for
+ * mmx_rollout_expert_record on a sim whose action_mode is not MMX_ACTION_ABS_POS. */
+int mmx_rollout_actions(mmx_sim* sim, const float* actions_dev, int32_t action_dim, int32_t n_env_steps,
+                        const mmx_trajectory* rec);
+int mmx_rollout_expert_record(mmx_sim* sim, int32_t n_env_steps, const mmx_trajectory* rec);
+
 /* Batched PNG encoder (dataset emission, generate_dataset.py:250-260: LeRobot embeds image
  * features as PNG files).  Encodes n RGB8 images (device, image i at rgb_dev + i * img_stride,
  * rows of 3 * width bytes, height <= 1024, width <= MMX_PNG_MAX_WIDTH: the encoder's row-above match

@@ -70,6 +70,19 @@ class MMXBuffers(C.Structure):
     ]
 
 
+class MMXTrajectory(C.Structure):
+    """mmx_trajectory (include/mmx_api.h): caller-owned device arrays [T][N][F], NULL = not recorded."""
+    _fields_ = [
+        ("obs", C.c_void_p), ("reward", C.c_void_p), ("done", C.c_void_p), ("reward_components", C.c_void_p),
+        ("target", C.c_void_p), ("episode_i", C.c_void_p), ("qpos", C.c_void_p), ("qvel", C.c_void_p),
+    ]
+
+
+# per-env width and dtype of every trajectory array
+TRAJ_FIELDS = {"obs": (NOBS, "float32"), "reward": (1, "float32"), "done": (3, "int32"),
+               "reward_components": (6, "float32"), "target": (4, "float32"), "episode_i": (EPI_N, "int32"),
+               "qpos": (NQ, "float32"), "qvel": (NV, "float32")}
+
 EXPORTED = ("mmx_config_default", "mmx_create", "mmx_destroy", "mmx_last_error", "mmx_reset", "mmx_step",
             "mmx_expert_plan", "mmx_rollout_expert", "mmx_physics_step", "mmx_forward", "mmx_get_buffers",
             "mmx_synchronize", "mmx_get_state", "mmx_set_state", "mmx_episode_seed", "mmx_rollout_lanes",
@@ -77,7 +90,7 @@ EXPORTED = ("mmx_config_default", "mmx_create", "mmx_destroy", "mmx_last_error",
             "mmx_kernel_times", "mmx_png_bound", "mmx_png_scratch", "mmx_png_encode", "mmx_png_pack", "mmx_image_stats",
             "mmx_queue_init", "mmx_queue_advance", "mmx_set_step_rows", "mmx_step_rows", "mmx_copy_ranges", "mmx_rollout_render_launches",
             "mmx_set_step_order", "mmx_step_order", "mmx_rollout_render_overlap", "mmx_set_render_effects",
-            "mmx_get_render_effects")
+            "mmx_get_render_effects", "mmx_rollout_actions", "mmx_rollout_expert_record")
 
 _lib = None
 
@@ -105,6 +118,8 @@ def load(build_if_missing: bool = True):
     L.mmx_step.argtypes = [vp, vp, C.c_int32]
     L.mmx_expert_plan.argtypes = [vp, C.c_int32, vp]
     L.mmx_rollout_expert.argtypes = [vp, C.c_int32]
+    L.mmx_rollout_actions.argtypes = [vp, vp, C.c_int32, C.c_int32, C.POINTER(MMXTrajectory)]
+    L.mmx_rollout_expert_record.argtypes = [vp, C.c_int32, C.POINTER(MMXTrajectory)]
     L.mmx_physics_step.argtypes = [vp, C.c_int32, C.c_int32]
     L.mmx_rollout_lanes.argtypes = [vp]
     L.mmx_rollout_lanes.restype = C.c_int
@@ -151,7 +166,7 @@ def load(build_if_missing: bool = True):
                  "mmx_forward", "mmx_get_buffers", "mmx_synchronize", "mmx_get_state", "mmx_set_state",
                  "mmx_expert_physics", "mmx_eval_reward", "mmx_kernel_timing", "mmx_kernel_times", "mmx_png_encode",
                  "mmx_png_pack", "mmx_image_stats", "mmx_queue_init", "mmx_queue_advance", "mmx_set_step_rows", "mmx_set_step_order",
-                 "mmx_set_render_effects"):
+                 "mmx_set_render_effects", "mmx_rollout_actions", "mmx_rollout_expert_record"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -292,8 +307,17 @@ class Sim:
         self._check(self.L.mmx_expert_plan(self.ptr, n_steps, C.c_void_p(action_ptr) if action_ptr else None),
                     "mmx_expert_plan")
 
-    def rollout_expert(self, n_env_steps: int):
-        self._check(self.L.mmx_rollout_expert(self.ptr, n_env_steps), "mmx_rollout_expert")
+    def rollout_expert(self, n_env_steps: int, record: MMXTrajectory | None = None):
+        """n_env_steps of the on-device expert; `record`: device arrays [T][N][F] that receive every step's outputs."""
+        if record is None:
+            self._check(self.L.mmx_rollout_expert(self.ptr, n_env_steps), "mmx_rollout_expert")
+        else:
+            self._check(self.L.mmx_rollout_expert_record(self.ptr, n_env_steps, C.byref(record)), "mmx_rollout_expert_record")
+
+    def rollout_actions(self, actions_ptr: int, action_dim: int, n_env_steps: int, record: MMXTrajectory | None = None):
+        """n_env_steps through the device actions [T][N][action_dim] in fused launches (mmx_rollout_actions)."""
+        self._check(self.L.mmx_rollout_actions(self.ptr, C.c_void_p(actions_ptr), action_dim, n_env_steps,
+                                               None if record is None else C.byref(record)), "mmx_rollout_actions")
 
     def kernel_timing(self, enable: bool):
         """Start (True: a new collection) / stop bracketing every rollout launch with HIP events."""

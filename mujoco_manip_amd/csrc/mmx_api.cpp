@@ -22,6 +22,10 @@ extern "C" hipError_t mmx_launch_step(const MMXState* S, const float* action, in
                                       int base, int count, int nsteps, hipStream_t st, const int* order);
 extern "C" hipError_t mmx_launch_step_l192(const MMXState* S, const float* action, int adim, int expert_autoreset,
                                            int base, int count, int nsteps, hipStream_t st, const int* order);
+extern "C" hipError_t mmx_launch_traj(const MMXState* S, const MMXTraj* R, const float* actions, int adim, int expert,
+                                      int base, int count, int nsteps, int k0, hipStream_t st, const int* order);
+extern "C" hipError_t mmx_launch_traj_l192(const MMXState* S, const MMXTraj* R, const float* actions, int adim, int expert,
+                                           int base, int count, int nsteps, int k0, hipStream_t st, const int* order);
 extern "C" hipError_t mmx_launch_order(const MMXState* S, int base, int count, int* order, int threads, hipStream_t st);
 extern "C" hipError_t mmx_launch_expert(const MMXState* S, int n, float* action, hipStream_t st);
 extern "C" hipError_t mmx_launch_physics(const MMXState* S, int n, int with_ik, hipStream_t st);
@@ -699,6 +703,88 @@ int mmx_rollout_expert(mmx_sim* sim, int32_t n_env_steps) {
       if (e == hipSuccess) e = j;
     }
   return hip_check(sim, e, "mmx_rollout_expert");
+}
+
+// The rollout of mmx_rollout_expert on the trajectory kernel: the same lanes, staggered plan, dispatch
+// order, fork / join and camera paths; every launch also gets the rollout step k0 its lane has reached,
+// which selects its action rows (expert = 0) and its slices of the record R.
+static int rollout_traj(mmx_sim* sim, const float* actions, int adim, int expert, int n, const mmx_trajectory* rec,
+                        const char* what) {
+  if (n == 0) return MMX_OK;
+  DeviceGuard guard(sim);
+  MMXTraj R{};
+  if (rec) R = MMXTraj{rec->obs, rec->reward, rec->done, rec->reward_components, rec->target, rec->episode_i, rec->qpos, rec->qvel};
+  const int N = sim->S.N, L = n > 1 ? rollout_lanes(sim) : 1;
+  auto launch = [&](const MMXState* S, int base, int count, int ns, int k0, hipStream_t st, const int* ord) {
+    return sim->step_rows == 192 ? mmx_launch_traj_l192(S, &R, actions, adim, expert, base, count, ns, k0, st, ord)
+                                 : mmx_launch_traj(S, &R, actions, adim, expert, base, count, ns, k0, st, ord);
+  };
+  hipError_t e = hipSuccess;
+  if (sim->render_overlap && sim->S.image_size > 0 && n > 1) {  // (mmx_rollout_expert's overlapped path)
+    hipStream_t rs = sim->rstream;
+    float* rp[2] = {sim->S.rpose, sim->rpose_alt};
+    for (int k = 0; k < n && e == hipSuccess; k++) {
+      MMXState Sk = sim->S;
+      Sk.rpose = rp[k & 1];
+      if (k >= 2) e = hipStreamWaitEvent(sim->stream, sim->ev_rend[k & 1], 0);
+      int* ord = sim->step_order ? sim->d_order : nullptr;
+      if (e == hipSuccess && ord) e = mmx_launch_order(&Sk, 0, N, ord, 1024, sim->stream);
+      if (e == hipSuccess) e = timed(sim, sim->stream, sim->t_step, [&] { return launch(&Sk, 0, N, 1, k, sim->stream, ord); });
+      if (e == hipSuccess) e = hipEventRecord(sim->ev_step, sim->stream);
+      if (e == hipSuccess) e = hipStreamWaitEvent(rs, sim->ev_step, 0);
+      if (e == hipSuccess) e = timed(sim, rs, sim->t_render, [&] { return mmx_launch_render(&Sk, 0, N, rs); });
+      if (e == hipSuccess) e = hipEventRecord(sim->ev_rend[k & 1], rs);
+    }
+    if (e == hipSuccess) e = hipStreamWaitEvent(sim->stream, sim->ev_rend[(n - 1) & 1], 0);
+    if (e == hipSuccess && ((n - 1) & 1)) std::swap(sim->S.rpose, sim->rpose_alt);
+    return hip_check(sim, e, what);
+  }
+  if (L > 1) {  // fork: every lane starts after the work already queued on the caller's stream
+    e = hipEventRecord(sim->ev_fork, sim->stream);
+    for (int l = 1; l < L && e == hipSuccess; l++) e = hipStreamWaitEvent(sim->lane[l], sim->ev_fork, 0);
+  }
+  std::vector<int> plan[mmx_sim::kMaxLanes];
+  int k0[mmx_sim::kMaxLanes] = {};  // the rollout step each lane's next launch starts at
+  size_t nl = 0;
+  for (int l = 0; l < L; l++) {
+    plan[l] = rollout_plan(sim, n, l);
+    nl = std::max(nl, plan[l].size());
+  }
+  for (size_t r = 0; r < nl && e == hipSuccess; r++) {
+    for (int l = 0; l < L && e == hipSuccess; l++) {
+      if (r >= plan[l].size()) continue;
+      const int ns = plan[l][r];
+      const int b0 = (int)((long)N * l / L), b1 = (int)((long)N * (l + 1) / L);
+      hipStream_t st = l ? sim->lane[l] : sim->stream;
+      int* ord = sim->step_order ? sim->d_order + b0 : nullptr;  // the lane's slice of the order buffer
+      if (ord) e = mmx_launch_order(&sim->S, b0, b1 - b0, ord, L > 1 ? 64 : 1024, st);
+      if (e == hipSuccess) e = timed(sim, st, sim->t_step, [&] { return launch(&sim->S, b0, b1 - b0, ns, k0[l], st, ord); });
+      k0[l] += ns;
+    }
+    if (e == hipSuccess && sim->S.image_size > 0)  // (L = 1, one step per launch: the render of that step)
+      e = timed(sim, sim->stream, sim->t_render, [&] { return mmx_launch_render(&sim->S, 0, N, sim->stream); });
+  }
+  if (L > 1)  // join: the caller's stream sees the whole rollout
+    for (int l = 1; l < L; l++) {
+      hipError_t j = hipEventRecord(sim->ev_join[l], sim->lane[l]);
+      if (j == hipSuccess) j = hipStreamWaitEvent(sim->stream, sim->ev_join[l], 0);
+      if (e == hipSuccess) e = j;
+    }
+  return hip_check(sim, e, what);
+}
+
+int mmx_rollout_actions(mmx_sim* sim, const float* actions_dev, int32_t action_dim, int32_t n_env_steps,
+                        const mmx_trajectory* rec) {
+  if (!sim || !actions_dev || n_env_steps < 0) return sim ? fail(sim, MMX_EINVAL, "mmx_rollout_actions: bad arguments") : MMX_EINVAL;
+  static const int kDim[5] = {4, 8, 10, 8, 10};
+  if (action_dim < kDim[sim->S.action_mode]) return fail(sim, MMX_EINVAL, "action_dim too small for action_mode");
+  return rollout_traj(sim, actions_dev, action_dim, 0, n_env_steps, rec, "mmx_rollout_actions");
+}
+
+int mmx_rollout_expert_record(mmx_sim* sim, int32_t n_env_steps, const mmx_trajectory* rec) {
+  if (!sim || n_env_steps < 0) return sim ? fail(sim, MMX_EINVAL, "mmx_rollout_expert_record: bad arguments") : MMX_EINVAL;
+  if (sim->S.action_mode != MMX_ACTION_ABS_POS) return fail(sim, MMX_EINVAL, "mmx_rollout_expert_record needs action_mode abs_pos");
+  return rollout_traj(sim, sim->expert_action, 4, 1, n_env_steps, rec, "mmx_rollout_expert_record");
 }
 
 int mmx_rollout_lanes(const mmx_sim* sim) { return sim ? rollout_lanes(sim) : 0; }

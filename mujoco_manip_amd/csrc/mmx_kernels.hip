@@ -3425,6 +3425,80 @@ MMX_NO_TAIL_MARK MMX_STEP_SYM(mmx_env_step_kernel)(MMXState S, const float* acti
   }
 }
 
+// The env's outputs after an env step, into slice `row` = step * N + env of the trajectory arrays.
+// Runs on the env's wave right after step_finish and needs no barrier of its own: the observation,
+// positions, velocities and target are read from the LDS record behind the SYNC() of store_obs /
+// store_env, by the lanes that stored them to the sim's buffers (after an autoreset: the new episode's);
+// reward, flags, components and the integer episode record were written to the sim's buffers by lane 0,
+// which reads its own stores back.  The helper wave (192 rows) has nothing to mirror.
+DEV void traj_record(const MMXState& S, const MMXTraj& R, int i, size_t row) {
+  const EnvSh& E = g_E;
+  if (R.obs)
+    for (int k = LANE; k < MMX_NOBS; k += WG) R.obs[row * MMX_NOBS + k] = obs_of(E)[k];
+  if (R.qpos && LANE < 30) R.qpos[row * 30 + LANE] = E.qpos[LANE];
+  if (R.qvel && LANE < 27) R.qvel[row * 27 + LANE] = E.qvel[LANE];
+  if (R.target && LANE < 4) R.target[row * 4 + LANE] = E.target[LANE];
+  if (LANE == 0) {
+    if (R.reward) R.reward[row] = S.reward[i];
+    if (R.done)
+      for (int k = 0; k < 3; k++) R.done[row * 3 + k] = S.done[3 * (size_t)i + k];
+    if (R.reward_components)
+      for (int k = 0; k < 6; k++) R.reward_components[row * 6 + k] = S.reward_components[(size_t)i * 6 + k];
+    if (R.epi)
+      for (int k = 0; k < EPI_N; k++) R.epi[row * EPI_N + k] = EPI(k);
+  }
+}
+
+// mmx_env_step_kernel's step loop with an action row per step and a per-step record (mmx_rollout_actions,
+// mmx_rollout_expert_record): step k of the launch is the rollout's step k0 + k; it reads the actions
+// [T][N][adim] at row k0 + k (expert = 1: planned in the kernel, as above) and, after step_finish, writes
+// the env's outputs to slice k0 + k of the arrays of R.  Each iteration is one single-step launch's body,
+// so states and records are bit-identical to a loop of mmx_step calls.  No per-phase profile here.
+extern "C" __global__ void __launch_bounds__(MMX_STEP_THREADS) __attribute__((amdgpu_waves_per_eu(MMX_STEP_WAVES, MMX_STEP_WAVES)))
+MMX_NO_TAIL_MARK MMX_STEP_SYM(mmx_env_traj_kernel)(MMXState S, MMXTraj R, const float* actions, int adim, int expert, int base,
+                                  int nsteps, int k0, const int* order) {
+  const int i = order ? order[blockIdx.x] : base + blockIdx.x;
+  if (i >= S.N) return;
+#if MMX_STEP_HELPER
+  if (threadIdx.x >= 64) {  // the helper wave, as in mmx_env_step_kernel (kept apart: that kernel's code stays as it
+                             // is); the record below adds no barrier to mirror
+    for (int k = 0; k < nsteps; k++) {
+      if (k) {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        XSYNC();
+      }
+      XSYNC();  // step_begin's record load
+      for (int sub = 0; sub < MMX_NSUBSTEP; sub++) {  // mj_step_wave's barriers C, K, A, P, Q
+        __syncthreads();
+        DELAY_HELPER();
+        ik_wave(g_E);
+        __syncthreads();  // K: the IK has read the kinematics cache; the env wave may overwrite it
+        __syncthreads();
+        DELAY_HELPER();
+        dynamics_wave(g_E);
+        __syncthreads();
+        collide_pairs(g_E, false, 2);
+        __syncthreads();
+      }
+    }
+    return;
+  }
+#endif
+  for (int k = 0; k < nsteps; k++) {
+    if (k) {  // the previous step's record stores complete before this step reloads it
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+      XSYNC();
+    }
+    const size_t step = (size_t)(k0 + k);
+    step_begin(S, i, expert ? actions : actions + step * (size_t)S.N * (size_t)adim, adim, expert);
+    XSYNC();
+    for (int sub = 0; sub < MMX_NSUBSTEP; sub++)
+      substep(S.solver_max_iter, S.solver_tol, sub == MMX_NSUBSTEP - 1 ? contacts_dst(S, i) : nullptr);
+    step_finish(S, i);
+    traj_record(S, R, i, step * (size_t)S.N + (size_t)i);
+  }
+}
+
 #ifndef MMX_STEP_ONLY
 // mj_forward position stage only (kinematics -> IK cache) + observation refresh
 extern "C" __global__ void __launch_bounds__(WG) mmx_forward_kernel(MMXState S) {
@@ -3666,6 +3740,15 @@ extern "C" hipError_t MMX_STEP_SYM(mmx_launch_step)(const MMXState* S, const flo
   if (nsteps > 1 && !expert) return hipErrorInvalidValue;  // host actions: one env step per launch
   hipLaunchKernelGGL(MMX_STEP_SYM(mmx_env_step_kernel), dim3(count), dim3(MMX_STEP_THREADS), step_lds_pad(), st, *S, action, adim, expert, base,
                      nsteps, order);
+  return hipGetLastError();
+}
+// `nsteps` env steps of envs [base, base+count) from the rollout's step k0 on, with per-step actions and record
+extern "C" hipError_t MMX_STEP_SYM(mmx_launch_traj)(const MMXState* S, const MMXTraj* R, const float* actions, int adim,
+                                                    int expert, int base, int count, int nsteps, int k0, hipStream_t st,
+                                                    const int* order) {
+  if (count <= 0 || nsteps <= 0) return hipSuccess;
+  hipLaunchKernelGGL(MMX_STEP_SYM(mmx_env_traj_kernel), dim3(count), dim3(MMX_STEP_THREADS), step_lds_pad(), st, *S, *R, actions, adim,
+                     expert, base, nsteps, k0, order);
   return hipGetLastError();
 }
 #ifndef MMX_STEP_ONLY

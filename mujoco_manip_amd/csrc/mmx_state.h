@@ -131,4 +131,17 @@ struct MMXState {
   unsigned int* bg_overhead;  // [Sg][Sg] the fixed overhead camera's background (packed RGB | seg << 24)
 };
 
+// Per-step record of a trajectory rollout (mmx_env_traj_kernel; mmx_trajectory of include/mmx_api.h):
+// caller-owned device arrays [T][N][F], slice k = the sim-owned buffer after env step k; null = not kept
+struct MMXTraj {
+  float* obs;                // [T][N][85]
+  float* reward;             // [T][N]
+  int* done;                 // [T][N][3]
+  float* reward_components;  // [T][N][6]
+  float* target;             // [T][N][4]
+  int* epi;                  // [T][N][EPI_N]
+  float* qpos;               // [T][N][30]
+  float* qvel;               // [T][N][27]
+};
+
 #endif

@@ -65,14 +65,18 @@ def episode_setup(metadata, episode_index: int):
     return seed, task, spawn_x, spawn_y
 
 
-def replay(dataset_root: str, episodes=None, action_key: str = "action.ee.pos_quat_g", device: int = 0):
+def replay(dataset_root: str, episodes=None, action_key: str = "action.ee.pos_quat_g", device: int = 0,
+           fused: bool = False):
     """Replay the recorded actions of `episodes` (default: all) in one batch.
 
     Returns dict with per-episode lists: target [T, 3], ee [T, 3], err [T], obs_state [T, 11]
-    (the post-step observation.state), plus the episodes' recorded frames for comparison."""
+    (the post-step observation.state), plus the episodes' recorded frames for comparison.
+    fused=True steps all frames with one PickPlaceVecEnv.rollout call (the observations come from its
+    per-step record) instead of one step() per frame: the same report, plus "sim_target" [T, 4] per
+    episode, the target and gripper value the simulator decoded from each action."""
     import torch
 
-    from .vec_env import PickPlaceVecEnv
+    from .vec_env import PickPlaceVecEnv, split_obs
 
     info, metadata, frames = read_lerobot_v3(dataset_root)
     ids = sorted(frames) if episodes is None else list(episodes)
@@ -106,16 +110,23 @@ def replay(dataset_root: str, episodes=None, action_key: str = "action.ee.pos_qu
         acts[len(a):, j] = a[-1]  # finished episodes hold their last action (not reported)
     acts_d = torch.as_tensor(acts, device=env.device)
     tgt, ee, st = [], [], []
+    if fused:
+        rec = env.rollout(acts_d, record=("obs", "target"))
+        state = split_obs(rec["obs"])["state"]
     for t in range(T_max):
-        obs, *_ = env.step(acts_d[t])
+        state_t = state[t] if fused else env.step(acts_d[t])[0]["state"]
         tgt.append(decode_targets(mode, acts_d[t], T_init))
-        ee.append(obs["state"][:, :3].to(torch.float64))
-        st.append(obs["state"])
+        ee.append(state_t[:, :3].to(torch.float64))
+        st.append(state_t)
     tgt = torch.stack(tgt).cpu().numpy()
     ee = torch.stack(ee).cpu().numpy()
     st = torch.stack(st).cpu().numpy()
+    if fused:
+        sim_tgt = rec["target"].cpu().numpy()
     env.close()
     out = {"episodes": ids, "mode": mode, "target": [], "ee": [], "err": [], "obs_state": [], "frames": frames}
+    if fused:
+        out["sim_target"] = [sim_tgt[:lengths[j], j] for j in range(n)]
     for j, e in enumerate(ids):
         L = lengths[j]
         out["target"].append(tgt[:L, j])
@@ -132,10 +143,11 @@ def main(argv=None):
     ap.add_argument("--episode-index", type=int, nargs="*", default=[0],
                     help="episodes to replay (-1 = all); the first one is printed frame by frame")
     ap.add_argument("--action-key", default="action.ee.pos_quat_g")
+    ap.add_argument("--fused", action="store_true", help="step all frames with one fused rollout call")
     a = ap.parse_args(argv)
     root = os.path.join(a.root, a.repo_id)
     eps = None if a.episode_index == [-1] else a.episode_index
-    r = replay(root, eps, a.action_key)
+    r = replay(root, eps, a.action_key, fused=a.fused)
     e0 = r["episodes"][0]
     print(f"Loaded episode {e0}: {len(r['err'][0])} frames; action key {a.action_key} -> mode {r['mode']}")
     print(f"{'Frame':>6}  {'Action XYZ':>30}  {'EE XYZ':>30}  {'Error':>8}")

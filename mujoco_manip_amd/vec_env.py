@@ -25,6 +25,11 @@ from . import _lib
 from .constants import ACTION_REPEAT, BINS, IMAGE_SIZE, MAX_EPISODE_STEPS, OBJECTS, OBS_SLICES, TASK_SETS, task_index
 
 
+def split_obs(flat: torch.Tensor) -> dict:
+    """The numeric observation keys of a flat observation [..., 85] (OBS_SLICES on the last axis), as views."""
+    return {k: flat[..., a:b].reshape(*flat.shape[:-1], *shape) for k, (a, b, shape) in OBS_SLICES.items()}
+
+
 class PickPlaceVecEnv:
     metadata = {"render_modes": [], "render_fps": 30}
 
@@ -135,6 +140,46 @@ class PickPlaceVecEnv:
     def rollout_expert(self, n_env_steps: int):
         """Device-resident FSM rollout (generate_dataset.py:140-196), no host round trips."""
         self.sim.rollout_expert(n_env_steps)
+
+    def rollout(self, actions: torch.Tensor | None = None, n_steps: int | None = None,
+                record=("obs", "reward", "done")) -> dict:
+        """T env steps in fused launches with a per-step record, no host round trips.
+
+        actions: [T, N, action_dim] fp32 on the GPU, one row per step and env (what T calls of step()
+        would be given); None: n_steps steps of the on-device FSM expert (abs_pos envs).  Returns
+        {name: tensor [T, N, ...]} for the names in `record` (_lib.TRAJ_FIELDS: obs, reward, done,
+        reward_components, target, episode_i, qpos, qvel): slice k is what the env's buffer holds after
+        step k, bit for bit what the step() loop gives ("obs" flat [T, N, 85]: split_obs; "done"
+        int32 [T, N, 3] = terminated, truncated, success).  The env ends in the loop's final state."""
+        names = (record,) if isinstance(record, str) else tuple(record or ())
+        for name in names:
+            if name not in _lib.TRAJ_FIELDS:
+                raise ValueError(f"record entries must be among {tuple(_lib.TRAJ_FIELDS)}, got '{name}'")
+        if actions is None:
+            if n_steps is None or int(n_steps) < 0:
+                raise ValueError("rollout needs actions [T, N, A] or n_steps >= 0 for the on-device expert")
+            T, a = int(n_steps), None
+        else:
+            a = torch.as_tensor(actions, dtype=torch.float32, device=self.device)
+            if a.dim() != 3 or a.shape[1] != self.num_envs or a.shape[2] < self.action_dim:
+                raise ValueError(f"actions must be [T, {self.num_envs}, {self.action_dim}], got {tuple(a.shape)}")
+            if n_steps is not None and int(n_steps) != a.shape[0]:
+                raise ValueError(f"n_steps {n_steps} does not match the {a.shape[0]} action rows")
+            T, a = a.shape[0], a.contiguous()
+        out, rec = {}, _lib.MMXTrajectory()
+        for name in names:
+            width, dtype = _lib.TRAJ_FIELDS[name]
+            shape = (T, self.num_envs, width) if width > 1 else (T, self.num_envs)
+            out[name] = torch.empty(shape, dtype=getattr(torch, dtype), device=self.device)
+            setattr(rec, name, out[name].data_ptr())
+        if T == 0:
+            return out
+        if a is None:
+            self.sim.rollout_expert(T, rec)
+        else:
+            self.sim.rollout_actions(a.data_ptr(), a.shape[2], T, rec)
+            self._last_action = a
+        return out
 
     @property
     def step_count(self) -> torch.Tensor:

@@ -19,6 +19,10 @@
 #   occupancy        C3 env steps/s with the envs per CU lowered by dynamic LDS per workgroup (MMX_LDS_PAD;
 #                    1,280-byte blocks, profiles/r05_lds_residency.json: 12,640 B = 12 per CU; pads 2560 /
 #                    6400 / 8960 / 20480 B -> 10 / 8 / 7 / 4 per CU)
+#   traj             action-sequence rollout timing (tools/traj_time.py): the step loop, the fused rollout with and
+#                    without its per-step record, the expert rollout with and without; BASELINE_LIB = a
+#                    library of the baseline commit adds its step loop (line a); TRAJ_OUT = a file for the
+#                    full result (the summary line goes to stdout either way)
 # Env: R (round tag, default r06), MMX_LIB_PATH (a library other than the product for every recipe).
 set -o pipefail
 cd ${GRAFT_REPO_ROOT:-$(pwd)}; ROOT=$(pwd); mkdir -p gpurun_out
@@ -120,6 +124,10 @@ dataset() {
   grep -h "frames_per_s" gpurun_out/${R}_dataset_bench_$1.json
 }
 
+traj() {
+  timeout -k 10 400 python -u tools/traj_time.py ${BASELINE_LIB:+--baseline-lib $BASELINE_LIB} ${TRAJ_OUT:+--out $TRAJ_OUT}
+}
+
 occupancy() {
   mkdir -p gpurun_out/occ
   local a="--steps 128 --warmup 32 --repeats 3 --no-cpu-baseline"
@@ -143,6 +151,7 @@ for recipe in "$@"; do
     dataset:*) dataset ${recipe#dataset:} ;;
     ab) bash tools/ab.sh ;;
     occupancy) occupancy ;;
+    traj) traj ;;
     *) echo "unknown recipe $recipe"; false ;;
   esac || exit $?
 done
