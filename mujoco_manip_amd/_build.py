@@ -15,9 +15,6 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libmmx.so")
 LIB_PROF = os.path.join(PKG, "libmmx_prof.so")
 SOURCES = ["mmx_kernels.hip", "mmx_step_l192.hip", "mmx_render.hip", "mmx_render_lit.hip", "mmx_png.hip", "mmx_api.cpp"]
-HEADERS = ["mmx_kernels.hip", "mmx_render.hip", "mmx_model_gen.h", "mmx_render_gen.h", "mmx_state.h", "mmx_device.h", "mmx_geom.h", "mmx_clock.h",
-           os.path.join("..", "..", "include", "mmx_api.h"),
-           os.path.join("..", "..", "include", "mmx_tuning.h")]
 ARCH = os.environ.get("MMX_OFFLOAD_ARCH", "gfx950")
 # device-code math: x / y as x * rcp(y) and sqrt without the denormal-scaling wrapper (v_rcp_f32 /
 # v_sqrt_f32, <= 1 ulp) instead of the correctly rounded fdiv / sqrt expansions (~10 VALU each).
@@ -64,7 +61,7 @@ TEST_VARIANTS = {
     # list-vs-full-prune bit-identity test)
     "libmmx_nolist.so": ["MMX_CAND_CAP=1"],
     # the 192-row kernel with one of its two waves held back after barriers C and A (MMX_HELPER_DELAY in
-    # mmx_kernels.hip: 1 the helper wave, 2 the env wave), and probe set 14 (full prunes and the list's
+    # mmx_step.inc: 1 the helper wave, 2 the env wave), and probe set 14 (full prunes and the list's
     # displacement bound in the stats): results may not depend on which wave is late
     "libmmx_hdelay.so": ["MMX_HELPER_DELAY=1", "MMX_PROBE=14"],
     "libmmx_edelay.so": ["MMX_HELPER_DELAY=2", "MMX_PROBE=14"],
@@ -76,38 +73,35 @@ def lib_path(profile: bool = False) -> str:
 
 
 def _stale(lib: str) -> bool:
+    """Any source-like file of csrc/ (sources, headers, the included step file) or public header newer than `lib`."""
     if not os.path.exists(lib):
         return True
     t = os.path.getmtime(lib)
-    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS]
-    return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
+    inc = os.path.join(PKG, "..", "include")
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".cpp", ".h", ".inc"))]
+    deps += [os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h")]
+    return any(os.path.getmtime(d) > t for d in deps)
 
 
-def _compile(src: str, profile: bool, verbose: bool) -> str:
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    obj = os.path.join(CSRC, os.path.splitext(src)[0] + ("_prof" if profile else "") + ".o")
-    cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-c", os.path.join(CSRC, src), "-o", obj]
-    cmd[1:1] = FLAGS + SOURCE_FLAGS.get(src, [])
-    if profile:
-        cmd.insert(1, "-DMMX_PHASE_CLOCK=1")
-        cmd.insert(1, f"-DMMX_PROBE={int(os.environ.get('MMX_PROBE', '1'))}")
-    if src.endswith(".cpp"):
-        cmd.insert(1, "-xhip")
+def _hipcc(src: str, obj: str, defines: list[str] | tuple = (), profile: bool = False, verbose: bool = False) -> str:
+    """Compile csrc/`src` into `obj`: the one place a hipcc compile command is put together (the product and
+    profile builds, TEST_VARIANTS and build_variant differ in `defines`, `profile` and the object's path only)."""
+    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + (["-xhip"] if src.endswith(".cpp") else [])
+    cmd += FLAGS + SOURCE_FLAGS.get(src, []) + [f"-D{d}" for d in defines] + (["-DMMX_PHASE_CLOCK=1"] if profile else [])
+    cmd += [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-c", os.path.join(CSRC, src), "-o", obj]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
     return obj
 
 
-def _compile_test_variant(name: str, src: str, verbose: bool) -> str:
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    obj = os.path.join(CSRC, os.path.splitext(src)[0] + "_" + os.path.splitext(name)[0] + ".o")
-    cmd = [hipcc] + FLAGS + SOURCE_FLAGS[src] + [f"-D{d}" for d in TEST_VARIANTS[name]] + [
-        f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-c", os.path.join(CSRC, src), "-o", obj]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    return obj
+def _link(out: str, objs: list[str]) -> str:
+    subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", out] + objs)
+    return out
+
+
+def _obj(src: str, tag: str = "") -> str:
+    return os.path.join(CSRC, os.path.splitext(src)[0] + tag + ".o")
 
 
 def build(force: bool = False, verbose: bool = False, profile: bool | None = False) -> str:
@@ -117,20 +111,20 @@ def build(force: bool = False, verbose: bool = False, profile: bool | None = Fal
     variants = [v for v in variants if force or _stale(lib_path(v))]
     tests = [n for n in TEST_VARIANTS if profile is None and (force or _stale(os.path.join(PKG, n)))]
     if variants or tests:
+        # the profile build's probe set: MMX_PROBE in the environment, 1 by default
+        pdef = [f"MMX_PROBE={int(os.environ.get('MMX_PROBE', '1'))}"]
         jobs = [(src, v) for v in variants for src in SOURCES]
         tjobs = [(n, src) for n in tests for src in STEP_SOURCES]
         with ThreadPoolExecutor(max_workers=min(HIPCC_JOBS, len(jobs) + len(tjobs))) as ex:
-            tobjs = [ex.submit(_compile_test_variant, n, src, verbose) for n, src in tjobs]
-            objs = list(ex.map(lambda j: _compile(j[0], j[1], verbose), jobs))
+            tobjs = [ex.submit(_hipcc, src, _obj(src, "_" + os.path.splitext(n)[0]), TEST_VARIANTS[n], False, verbose)
+                     for n, src in tjobs]
+            objs = list(ex.map(lambda j: _hipcc(j[0], _obj(j[0], "_prof" if j[1] else ""), pdef if j[1] else [], j[1], verbose), jobs))
             tobjs = [f.result() for f in tobjs]
-        hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
         for v in variants:
-            mine = [o for o, (_, vv) in zip(objs, jobs) if vv == v]
-            subprocess.check_call([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", lib_path(v)] + mine)
+            _link(lib_path(v), [o for o, (_, vv) in zip(objs, jobs) if vv == v])
         for n in tests:  # the variant's step kernels + the product's objects of the other sources
             kobjs = [o for o, (nn, _) in zip(tobjs, tjobs) if nn == n]
-            rest = [os.path.join(CSRC, os.path.splitext(src)[0] + ".o") for src in SOURCES if src not in STEP_SOURCES]
-            subprocess.check_call([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", os.path.join(PKG, n)] + kobjs + rest)
+            _link(os.path.join(PKG, n), kobjs + [_obj(src) for src in SOURCES if src not in STEP_SOURCES])
     return lib_path(bool(profile))
 
 
@@ -141,20 +135,9 @@ if __name__ == "__main__":
 def build_variant(out: str, defines: list[str], profile: bool = True) -> str:
     """Diagnostic / experiment build of the same sources with extra -D defines into `out`
     (e.g. build/libmmx_prof5.so for probe set 5); loaded with MMX_LIB_PATH.  Not the product."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     tag = os.path.splitext(os.path.basename(out))[0]
-    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-
-    def one(src):
-        obj = os.path.join(os.path.dirname(os.path.abspath(out)), f"{tag}_{os.path.splitext(src)[0]}.o")
-        cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-c", os.path.join(CSRC, src), "-o", obj]
-        cmd[1:1] = FLAGS + SOURCE_FLAGS.get(src, []) + [f"-D{d}" for d in defines] + (["-DMMX_PHASE_CLOCK=1"] if profile else [])
-        if src.endswith(".cpp"):
-            cmd.insert(1, "-xhip")
-        subprocess.check_call(cmd)
-        return obj
-
+    where = os.path.dirname(os.path.abspath(out))
+    os.makedirs(where, exist_ok=True)
     with ThreadPoolExecutor(max_workers=len(SOURCES)) as ex:
-        objs = list(ex.map(one, SOURCES))
-    subprocess.check_call([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", out] + objs)
-    return out
+        objs = list(ex.map(lambda src: _hipcc(src, os.path.join(where, f"{tag}_{os.path.splitext(src)[0]}.o"), defines, profile), SOURCES))
+    return _link(out, objs)

@@ -489,12 +489,18 @@ int mmx_reset(mmx_sim* sim, const uint64_t* seeds, const uint8_t* seed_given, co
 }
 
 namespace {
-static hipError_t launch_step(const mmx_sim* sim, const float* action, int adim, int expert, int base, int count, int nsteps,
-                              hipStream_t st, const int* order = nullptr, const MMXState* S = nullptr) {
-  if (!S) S = &sim->S;
-  return sim->step_rows == 192 ? mmx_launch_step_l192(S, action, adim, expert, base, count, nsteps, st, order)
-                               : mmx_launch_step(S, action, adim, expert, base, count, nsteps, st, order);
+// the step kernels' launchers of the sim's LDS-row layout (mmx_step.inc is built at 128 and at 192 rows):
+// the one place the layout is chosen, for mmx_step and the rollouts
+struct StepLaunchers {
+  decltype(&mmx_launch_step) step;
+  decltype(&mmx_launch_traj) traj;
+};
+StepLaunchers step_launchers(const mmx_sim* sim) {
+  return sim->step_rows == 192 ? StepLaunchers{mmx_launch_step_l192, mmx_launch_traj_l192}
+                               : StepLaunchers{mmx_launch_step, mmx_launch_traj};
 }
+// floats per env that each action mode's action needs
+constexpr int kDim[5] = {4, 8, 10, 8, 10};
 }  // namespace
 
 int mmx_set_step_rows(mmx_sim* sim, int32_t rows) {
@@ -513,13 +519,12 @@ int mmx_step_order(const mmx_sim* sim) { return sim ? sim->step_order : -1; }
 int mmx_step(mmx_sim* sim, const float* action_dev, int32_t action_dim) {
   if (!sim || !action_dev) return MMX_EINVAL;
   DeviceGuard guard(sim);
-  static const int kDim[5] = {4, 8, 10, 8, 10};
   if (action_dim < kDim[sim->S.action_mode]) return fail(sim, MMX_EINVAL, "action_dim too small for action_mode");
   // longest first by FSM phase (the expert's plan keeps it current; with policy actions it stays idle
   // and the order is index order up to ties)
   int* ord = sim->step_order ? sim->d_order : nullptr;
   hipError_t e = ord ? mmx_launch_order(&sim->S, 0, sim->S.N, ord, 1024, sim->stream) : hipSuccess;
-  if (e == hipSuccess) e = launch_step(sim, action_dev, action_dim, 0, 0, sim->S.N, 1, sim->stream, ord);
+  if (e == hipSuccess) e = step_launchers(sim).step(&sim->S, action_dev, action_dim, 0, 0, sim->S.N, 1, sim->stream, ord);
   if (e == hipSuccess) e = mmx_launch_render(&sim->S, 0, sim->S.N, sim->stream);
   return hip_check(sim, e, "mmx_step");
 }
@@ -588,139 +593,73 @@ static int rollout_len(const mmx_sim* sim, int n) {
 // lanes of a rollout: with cameras one (every step ends in the render over all envs, and one launch
 // orders all envs longest-first: C5 +2.0 % over 4 lanes)
 static int rollout_lanes(const mmx_sim* sim) { return sim->S.image_size > 0 ? 1 : sim->nlanes; }
-// Launch lengths of lane `lane` for an n-step rollout (above); env MMX_PLAN = "a,b,...[;c,d,...]" per
-// lane (the last list repeats for the lanes after it) overrides it for experiments when its lengths sum
-// to n.
-static std::vector<int> rollout_plan(const mmx_sim* sim, int n, int lane) {
-  std::vector<int> v;
-  if (const char* e = std::getenv("MMX_PLAN")) {
-    std::string all(e), mine;
-    size_t pos = 0;
-    for (int l = 0;; l++) {
-      const size_t sc = all.find(';', pos);
-      mine = all.substr(pos, sc == std::string::npos ? std::string::npos : sc - pos);
-      if (l == lane || sc == std::string::npos) break;
-      pos = sc + 1;
+// Launch lengths of every lane for an n-step rollout (above): `lanes` of them (one for a single step),
+// `rounds` = the most launches any lane makes.  Env MMX_PLAN = "a,b,...[;c,d,...]" per lane (the last
+// list repeats for the lanes after it) overrides a lane's lengths for experiments when they sum to n.
+struct RolloutPlan {
+  int lanes = 0;
+  size_t rounds = 0;
+  std::vector<int> len[mmx_sim::kMaxLanes];
+};
+static RolloutPlan rollout_plan(const mmx_sim* sim, int n) {
+  RolloutPlan P;
+  P.lanes = n > 1 ? rollout_lanes(sim) : 1;
+  const char* env = std::getenv("MMX_PLAN");
+  for (int lane = 0; lane < P.lanes; lane++) {
+    std::vector<int>& v = P.len[lane];
+    if (env) {
+      std::string all(env), mine;
+      size_t pos = 0;
+      for (int l = 0;; l++) {
+        const size_t sc = all.find(';', pos);
+        mine = all.substr(pos, sc == std::string::npos ? std::string::npos : sc - pos);
+        if (l == lane || sc == std::string::npos) break;
+        pos = sc + 1;
+      }
+      int sum = 0;
+      for (size_t a = 0; a < mine.size();) {
+        const int k = std::atoi(mine.c_str() + a);
+        if (k <= 0) break;
+        v.push_back(k);
+        sum += k;
+        const size_t c = mine.find(',', a);
+        if (c == std::string::npos) break;
+        a = c + 1;
+      }
+      if (sum != n) v.clear();
     }
-    int sum = 0;
-    for (size_t a = 0; a < mine.size();) {
-      const int k = std::atoi(mine.c_str() + a);
-      if (k <= 0) break;
-      v.push_back(k);
-      sum += k;
-      const size_t c = mine.find(',', a);
-      if (c == std::string::npos) break;
-      a = c + 1;
+    if (v.empty() && n > 0) {
+      const int len = rollout_len(sim, n), L = rollout_lanes(sim);
+      int rem = n;
+      const int first = std::min(rem, lane * len / std::max(L, 1));
+      if (first > 0) {
+        v.push_back(first);
+        rem -= first;
+      }
+      for (; rem > 0; rem -= std::min(rem, len)) v.push_back(std::min(rem, len));
     }
-    if (sum == n) return v;
-    v.clear();
+    P.rounds = std::max(P.rounds, v.size());
   }
-  if (n <= 0) return v;
-  const int len = rollout_len(sim, n), L = rollout_lanes(sim);
-  int rem = n;
-  const int first = std::min(rem, lane * len / std::max(L, 1));
-  if (first > 0) {
-    v.push_back(first);
-    rem -= first;
-  }
-  for (; rem > 0; rem -= std::min(rem, len)) v.push_back(std::min(rem, len));
-  return v;
-}
-// the most launches any lane makes
-static int rollout_launches(const mmx_sim* sim, int n) {
-  size_t m = 0;
-  for (int l = 0; l < rollout_lanes(sim); l++) m = std::max(m, rollout_plan(sim, n, l).size());
-  return (int)m;
+  return P;
 }
 int mmx_rollout_launches(const mmx_sim* sim, int32_t n_env_steps) {
-  return sim ? rollout_launches(sim, n_env_steps) : 0;
+  return sim ? (int)rollout_plan(sim, n_env_steps).rounds : 0;
 }
-int mmx_rollout_expert(mmx_sim* sim, int32_t n_env_steps) {
-  if (!sim || sim->S.action_mode != MMX_ACTION_ABS_POS) return MMX_EINVAL;
+// The rollout's choreography, once, for both step kernels: `launch(S, base, count, nsteps, k0, st, order)`
+// launches `nsteps` env steps of envs [base, base + count) on `st`, k0 = the rollout step that lane has
+// reached (the trajectory kernel's action rows and record slices; the step kernel ignores it).  `what`
+// names the entry point in the error text.  (A template, not std::function: the launch is inlined.)
+extern "C++" {
+template <class Launch>
+static int rollout(mmx_sim* sim, int n, const char* what, Launch launch) {
+  if (n <= 0) return MMX_OK;
   DeviceGuard guard(sim);
-  const int N = sim->S.N, L = n_env_steps > 1 ? rollout_lanes(sim) : 1;
+  const int N = sim->S.N;
   hipError_t e = hipSuccess;
-  if (sim->render_overlap && sim->S.image_size > 0 && n_env_steps > 1) {
+  if (sim->render_overlap && sim->S.image_size > 0 && n > 1) {
     // the render of step k on its own stream beside the step k + 1 on the caller's stream (a render
     // workgroup's 80 KB of LDS fits a CU the step launch's tail has half emptied: C5 +6.6 %, DESIGN
     // §8 f1); step k writes the pose buffer render k - 2 read, so it waits for that render only
-    hipStream_t rs = sim->rstream;
-    float* rp[2] = {sim->S.rpose, sim->rpose_alt};
-    for (int k = 0; k < n_env_steps && e == hipSuccess; k++) {
-      MMXState Sk = sim->S;
-      Sk.rpose = rp[k & 1];
-      if (k >= 2) e = hipStreamWaitEvent(sim->stream, sim->ev_rend[k & 1], 0);
-      int* ord = sim->step_order ? sim->d_order : nullptr;
-      if (e == hipSuccess && ord) e = mmx_launch_order(&Sk, 0, N, ord, 1024, sim->stream);
-      if (e == hipSuccess)
-        e = timed(sim, sim->stream, sim->t_step,
-                  [&] { return launch_step(sim, sim->expert_action, 4, 1, 0, N, 1, sim->stream, ord, &Sk); });
-      if (e == hipSuccess) e = hipEventRecord(sim->ev_step, sim->stream);
-      if (e == hipSuccess) e = hipStreamWaitEvent(rs, sim->ev_step, 0);
-      if (e == hipSuccess) e = timed(sim, rs, sim->t_render, [&] { return mmx_launch_render(&Sk, 0, N, rs); });
-      if (e == hipSuccess) e = hipEventRecord(sim->ev_rend[k & 1], rs);
-    }
-    // the caller's stream sees the last render; S.rpose names the newest poses
-    if (e == hipSuccess) e = hipStreamWaitEvent(sim->stream, sim->ev_rend[(n_env_steps - 1) & 1], 0);
-    if (e == hipSuccess && ((n_env_steps - 1) & 1)) std::swap(sim->S.rpose, sim->rpose_alt);
-    return hip_check(sim, e, "mmx_rollout_expert");
-  }
-  if (L > 1) {  // fork: every lane starts after the work already queued on the caller's stream
-    e = hipEventRecord(sim->ev_fork, sim->stream);
-    for (int l = 1; l < L && e == hipSuccess; l++) e = hipStreamWaitEvent(sim->lane[l], sim->ev_fork, 0);
-  }
-  // the step kernel plans with the FSM itself (expert=1); step k of range l only depends on step
-  // k-1 of range l.  Without cameras a launch runs up to `fuse` consecutive steps of its envs
-  // (mmx_rollout_steps_per_launch); with cameras every step is rendered, one step per launch.
-  std::vector<int> plan[mmx_sim::kMaxLanes];
-  size_t nl = 0;
-  for (int l = 0; l < L; l++) {
-    plan[l] = rollout_plan(sim, n_env_steps, l);
-    nl = std::max(nl, plan[l].size());
-  }
-  // with cameras (L = 1): the step of all envs, then ONE render launch over all envs (the render's
-  // 80 KB workgroups cannot share a CU with the step kernel's: a render per lane beside the other
-  // lanes' steps ran as a trickle, C5 -2.8 %, DESIGN §8 f1)
-  for (size_t r = 0; r < nl && e == hipSuccess; r++) {
-    for (int l = 0; l < L && e == hipSuccess; l++) {
-      if (r >= plan[l].size()) continue;
-      const int ns = plan[l][r];
-      const int b0 = (int)((long)N * l / L), b1 = (int)((long)N * (l + 1) / L);
-      hipStream_t st = l ? sim->lane[l] : sim->stream;
-      int* ord = sim->step_order ? sim->d_order + b0 : nullptr;  // the lane's slice of the order buffer
-      if (ord) e = mmx_launch_order(&sim->S, b0, b1 - b0, ord, L > 1 ? 64 : 1024, st);
-      if (e == hipSuccess)
-        e = timed(sim, st, sim->t_step,
-                  [&] { return launch_step(sim, sim->expert_action, 4, 1, b0, b1 - b0, ns, st, ord); });
-    }
-    if (e == hipSuccess && sim->S.image_size > 0)
-      e = timed(sim, sim->stream, sim->t_render, [&] { return mmx_launch_render(&sim->S, 0, N, sim->stream); });
-  }
-  if (L > 1)  // join: the caller's stream sees the whole rollout, as with a single launch chain
-    for (int l = 1; l < L; l++) {
-      hipError_t j = hipEventRecord(sim->ev_join[l], sim->lane[l]);
-      if (j == hipSuccess) j = hipStreamWaitEvent(sim->stream, sim->ev_join[l], 0);
-      if (e == hipSuccess) e = j;
-    }
-  return hip_check(sim, e, "mmx_rollout_expert");
-}
-
-// The rollout of mmx_rollout_expert on the trajectory kernel: the same lanes, staggered plan, dispatch
-// order, fork / join and camera paths; every launch also gets the rollout step k0 its lane has reached,
-// which selects its action rows (expert = 0) and its slices of the record R.
-static int rollout_traj(mmx_sim* sim, const float* actions, int adim, int expert, int n, const mmx_trajectory* rec,
-                        const char* what) {
-  if (n == 0) return MMX_OK;
-  DeviceGuard guard(sim);
-  MMXTraj R{};
-  if (rec) R = MMXTraj{rec->obs, rec->reward, rec->done, rec->reward_components, rec->target, rec->episode_i, rec->qpos, rec->qvel};
-  const int N = sim->S.N, L = n > 1 ? rollout_lanes(sim) : 1;
-  auto launch = [&](const MMXState* S, int base, int count, int ns, int k0, hipStream_t st, const int* ord) {
-    return sim->step_rows == 192 ? mmx_launch_traj_l192(S, &R, actions, adim, expert, base, count, ns, k0, st, ord)
-                                 : mmx_launch_traj(S, &R, actions, adim, expert, base, count, ns, k0, st, ord);
-  };
-  hipError_t e = hipSuccess;
-  if (sim->render_overlap && sim->S.image_size > 0 && n > 1) {  // (mmx_rollout_expert's overlapped path)
     hipStream_t rs = sim->rstream;
     float* rp[2] = {sim->S.rpose, sim->rpose_alt};
     for (int k = 0; k < n && e == hipSuccess; k++) {
@@ -735,25 +674,28 @@ static int rollout_traj(mmx_sim* sim, const float* actions, int adim, int expert
       if (e == hipSuccess) e = timed(sim, rs, sim->t_render, [&] { return mmx_launch_render(&Sk, 0, N, rs); });
       if (e == hipSuccess) e = hipEventRecord(sim->ev_rend[k & 1], rs);
     }
+    // the caller's stream sees the last render; S.rpose names the newest poses
     if (e == hipSuccess) e = hipStreamWaitEvent(sim->stream, sim->ev_rend[(n - 1) & 1], 0);
     if (e == hipSuccess && ((n - 1) & 1)) std::swap(sim->S.rpose, sim->rpose_alt);
     return hip_check(sim, e, what);
   }
+  // step k of range l only depends on step k-1 of range l.  Without cameras a launch runs up to `fuse`
+  // consecutive steps of its envs (mmx_rollout_steps_per_launch); with cameras every step is rendered,
+  // one step per launch.
+  const RolloutPlan P = rollout_plan(sim, n);
+  const int L = P.lanes;
   if (L > 1) {  // fork: every lane starts after the work already queued on the caller's stream
     e = hipEventRecord(sim->ev_fork, sim->stream);
     for (int l = 1; l < L && e == hipSuccess; l++) e = hipStreamWaitEvent(sim->lane[l], sim->ev_fork, 0);
   }
-  std::vector<int> plan[mmx_sim::kMaxLanes];
   int k0[mmx_sim::kMaxLanes] = {};  // the rollout step each lane's next launch starts at
-  size_t nl = 0;
-  for (int l = 0; l < L; l++) {
-    plan[l] = rollout_plan(sim, n, l);
-    nl = std::max(nl, plan[l].size());
-  }
-  for (size_t r = 0; r < nl && e == hipSuccess; r++) {
+  // with cameras (L = 1): the step of all envs, then ONE render launch over all envs (the render's
+  // 80 KB workgroups cannot share a CU with the step kernel's: a render per lane beside the other
+  // lanes' steps ran as a trickle, C5 -2.8 %, DESIGN §8 f1)
+  for (size_t r = 0; r < P.rounds && e == hipSuccess; r++) {
     for (int l = 0; l < L && e == hipSuccess; l++) {
-      if (r >= plan[l].size()) continue;
-      const int ns = plan[l][r];
+      if (r >= P.len[l].size()) continue;
+      const int ns = P.len[l][r];
       const int b0 = (int)((long)N * l / L), b1 = (int)((long)N * (l + 1) / L);
       hipStream_t st = l ? sim->lane[l] : sim->stream;
       int* ord = sim->step_order ? sim->d_order + b0 : nullptr;  // the lane's slice of the order buffer
@@ -761,10 +703,10 @@ static int rollout_traj(mmx_sim* sim, const float* actions, int adim, int expert
       if (e == hipSuccess) e = timed(sim, st, sim->t_step, [&] { return launch(&sim->S, b0, b1 - b0, ns, k0[l], st, ord); });
       k0[l] += ns;
     }
-    if (e == hipSuccess && sim->S.image_size > 0)  // (L = 1, one step per launch: the render of that step)
+    if (e == hipSuccess && sim->S.image_size > 0)
       e = timed(sim, sim->stream, sim->t_render, [&] { return mmx_launch_render(&sim->S, 0, N, sim->stream); });
   }
-  if (L > 1)  // join: the caller's stream sees the whole rollout
+  if (L > 1)  // join: the caller's stream sees the whole rollout, as with a single launch chain
     for (int l = 1; l < L; l++) {
       hipError_t j = hipEventRecord(sim->ev_join[l], sim->lane[l]);
       if (j == hipSuccess) j = hipStreamWaitEvent(sim->stream, sim->ev_join[l], 0);
@@ -772,11 +714,33 @@ static int rollout_traj(mmx_sim* sim, const float* actions, int adim, int expert
     }
   return hip_check(sim, e, what);
 }
+}  // extern "C++"
+
+// The step kernel plans with the FSM itself (expert = 1) and writes no record.
+int mmx_rollout_expert(mmx_sim* sim, int32_t n_env_steps) {
+  if (!sim || sim->S.action_mode != MMX_ACTION_ABS_POS) return MMX_EINVAL;
+  const auto step = step_launchers(sim).step;
+  return rollout(sim, n_env_steps, "mmx_rollout_expert",
+                 [&](const MMXState* S, int base, int count, int ns, int, hipStream_t st, const int* ord) {
+                   return step(S, sim->expert_action, 4, 1, base, count, ns, st, ord);
+                 });
+}
+
+// The same rollout on the trajectory kernel: every launch also gets the rollout step k0 its lane has
+// reached, which selects its action rows (expert = 0) and its slices of the record `rec`.
+static int rollout_traj(mmx_sim* sim, const float* actions, int adim, int expert, int n, const mmx_trajectory* rec,
+                        const char* what) {
+  MMXTraj R{};
+  if (rec) R = MMXTraj{rec->obs, rec->reward, rec->done, rec->reward_components, rec->target, rec->episode_i, rec->qpos, rec->qvel};
+  const auto traj = step_launchers(sim).traj;
+  return rollout(sim, n, what, [&](const MMXState* S, int base, int count, int ns, int k0, hipStream_t st, const int* ord) {
+    return traj(S, &R, actions, adim, expert, base, count, ns, k0, st, ord);
+  });
+}
 
 int mmx_rollout_actions(mmx_sim* sim, const float* actions_dev, int32_t action_dim, int32_t n_env_steps,
                         const mmx_trajectory* rec) {
   if (!sim || !actions_dev || n_env_steps < 0) return sim ? fail(sim, MMX_EINVAL, "mmx_rollout_actions: bad arguments") : MMX_EINVAL;
-  static const int kDim[5] = {4, 8, 10, 8, 10};
   if (action_dim < kDim[sim->S.action_mode]) return fail(sim, MMX_EINVAL, "action_dim too small for action_mode");
   return rollout_traj(sim, actions_dev, action_dim, 0, n_env_steps, rec, "mmx_rollout_actions");
 }

@@ -368,3 +368,47 @@ def test_fused_replay_equals_loop(tmp_path):
         # the simulator's own decode of each action is the report's target (fp32 against fp64 arithmetic)
         for x, y in zip(fused["sim_target"], fused["target"]):
             assert x.shape == (len(y), 4) and np.abs(x[:, :3] - y).max() < 1e-5
+
+
+# ------------------------------------------------------------------ 8. one rollout driver
+def _lane_launches(n, fuse, lanes):
+    """Launches each lane makes for n steps (mmx_api.cpp rollout_plan, as _plan_launches in tests/test_gpu.py):
+    len = min(fuse, ceil(n / 4)); lane l starts with l * len / lanes steps, then launches of len, then the rest."""
+    ln = max(1, min(fuse, -(-n // 4)))
+    firsts = [min(n, l * ln // lanes) for l in range(lanes)]
+    return [(1 if f else 0) + -(-(n - f) // ln) for f in firsts]
+
+
+@pytest.mark.parametrize("case", ["lanes", "cameras_overlapped", "cameras_serial"])
+def test_both_rollout_families_make_the_plans_launches(case, monkeypatch):
+    """mmx_rollout_expert (the step kernel) and mmx_rollout_expert_record (the trajectory kernel) go through
+    one driver: both make the step and render launches the plan defines, counted by the launch timing.
+    lanes: 10 envs on four lanes, launches of at most 3 steps, 11 steps: uneven env slices, lanes 2 and 3
+    start with a short launch, every lane ends with a remainder.  cameras: one lane, a step launch and a
+    render launch per step; 3 steps end the overlapped path on the alternate pose buffer."""
+    from mujoco_manip_amd import _lib
+
+    if case == "lanes":
+        monkeypatch.setenv("MMX_FUSE", "3")
+        n, T, image_size, fuse, lanes = 10, 11, 0, 3, 4
+    else:
+        monkeypatch.setenv("MMX_RENDER_OVERLAP", "1" if case == "cameras_overlapped" else "0")
+        n, T, image_size, fuse, lanes = 4, 3, 32, 1, 1
+    per_lane = _lane_launches(T, fuse, lanes)
+    if case == "lanes":
+        assert per_lane == [4, 4, 5, 4]  # 3,3,3,2 / 3,3,3,2 / 1,3,3,3,1 / 2,3,3,3
+    counts = []
+    for record in (None, _lib.MMXTrajectory()):
+        env = make_env(n=n, image_size=image_size)
+        assert env.sim.rollout_lanes == lanes and env.sim.rollout_launches(T) == max(per_lane)
+        if image_size:
+            assert env.sim.rollout_render_overlap == (case == "cameras_overlapped")
+        env.sim.kernel_timing(True)
+        env.sim.rollout_expert(T, record)
+        env.sim.kernel_timing(False)
+        kt = env.sim.kernel_times()
+        counts.append((kt["step_launches"], kt["render_launches"]))
+        env.close()
+    renders = T if image_size else 0  # one render launch over all envs after every step
+    print(case, "step / render launches:", counts, "plan:", (sum(per_lane), renders))
+    assert counts[0] == counts[1] == (sum(per_lane), renders)

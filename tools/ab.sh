@@ -2,8 +2,9 @@
 # Parameterised A/B runner for experiment builds (tools/ab_build.py -> build/libmmx_<name>.so), run on
 # the GPU box.  Replaces the r01-r03 one-off gpu_*.sh / render_ab*.sh scripts.
 #   LIBS="build/libmmx_a.so build/libmmx_b.so"  builds to compare (the product libmmx.so is always first)
-#   ROUNDS=3        interleaved bench rounds (C3 line: --steps STEPS --warmup 32 --repeats 1)
+#   ROUNDS=3        interleaved bench rounds (C3 line: --steps STEPS --warmup WARMUP --repeats 1)
 #   STEPS=512       timed env steps per bench run
+#   WARMUP=32       warm-up env steps per bench run (the driver's configuration: STEPS=20 WARMUP=5)
 #   WORKLOAD=c3     bench workload
 #   TESTS=0|1       run the GPU parity suite with every library first (stops at the first failure)
 #   PMC=0|1         one SQ counter pass per library (VALU, LDS bank conflicts, active lanes)
@@ -22,7 +23,7 @@ fi
 for r in $(seq 1 ${ROUNDS:-3}); do for lib in $ALL; do
   n=$(basename $lib .so)
   MMX_LIB_PATH=$lib timeout -k 10 300 python -u bench.py --workload ${WORKLOAD:-c3} --no-cpu-baseline \
-    --steps ${STEPS:-512} --warmup 32 --repeats 1 --full > $OUT/bench_$n.log 2>&1 || { tail -5 $OUT/bench_$n.log; exit 1; }
+    --steps ${STEPS:-512} --warmup ${WARMUP:-32} --repeats 1 --full > $OUT/bench_$n.log 2>&1 || { tail -5 $OUT/bench_$n.log; exit 1; }
   echo "$n $(grep -h '^{' $OUT/bench_$n.log)" >> $OUT/ab.txt
 done; done
 if [ "${PMC:-0}" = 1 ]; then

@@ -1,8 +1,10 @@
 """Scratch frames and spill instructions of the step kernel's functions in a hipcc -S listing: the
 evidence behind the HBM traffic of the out-of-line substep.  Usage:
     hipcc ... --cuda-device-only -S mmx_kernels.hip -o k.s ; python tools/isa_frame.py k.s [k2.s]
+(mmx_kernels.hip holds the 128-row step kernels through mmx_step.inc, mmx_step_l192.hip the 192-row ones.)
 Per function: private segment bytes per lane, VGPRs, scratch stores / loads (the callee-saved save
-area and spills), v_writelane / v_readlane (SGPR spills into VGPR lanes and cross-lane reads)."""
+area and spills), v_writelane / v_readlane (SGPR spills into VGPR lanes and cross-lane reads).
+functions() is the listing splitter, shared with tools/isa_same.py."""
 import collections
 import re
 import sys
@@ -10,20 +12,34 @@ import sys
 FUNCS = ("_Z7substepifPf", "mmx_env_step_kernel", "mmx_env_step_kernel_l192", "_Z10step_beginRK8MMXStateiPKfii",
          "_Z11step_finishRK8MMXStatei")  # (a listing holds one of the two kernels: the other is left out)
 
+# a function's label: `name:` in a -S listing, `0000000000001900 <name>:` in llvm-objdump -d output
+LABEL = re.compile(r"^(?:[0-9a-f]+ <)?([A-Za-z_][\w.$]*)>?:\s*(;.*)?$")
+
+
+def functions(txt):
+    """(function, line) for every non-empty line below a function's label, local labels included."""
+    fn, in_text = None, True
+    for line in txt.split("\n"):
+        d = line.split()[0] if line.strip() else ""
+        if d in (".section", ".amdgpu_metadata", ".text", ".data", ".bss", ".rodata"):  # data sections and notes are no function's lines
+            in_text = d == ".text" or (d == ".section" and ".text" in line)
+            continue
+        m = LABEL.match(line)
+        if m and in_text and not m.group(1).startswith((".L", "$")):
+            fn = m.group(1)
+            continue
+        if fn and in_text and line.strip():
+            yield fn, line
+
 
 def frames(path):
     txt = open(path).read()
-    ops, fn = collections.defaultdict(collections.Counter), None
-    for line in txt.split("\n"):
-        m = re.match(r"^([A-Za-z_][\w.$]*):\s*(;.*)?$", line)
-        if m and not m.group(1).startswith((".L", "$")):
-            fn = m.group(1)
-            continue
+    ops = collections.defaultdict(collections.Counter)
+    for fn, line in functions(txt):
         t = line.strip().split()
-        if fn and t:
-            for k in ("scratch_store", "scratch_load", "v_writelane", "v_readlane"):
-                if t[0].startswith(k):
-                    ops[fn][k] += 1
+        for k in ("scratch_store", "scratch_load", "v_writelane", "v_readlane"):
+            if t[0].startswith(k):
+                ops[fn][k] += 1
     out = {}
     for f in FUNCS:
         seg = re.search(rf"\.set (?:\.L)?{re.escape(f)}\.private_seg_size, (\d+)(\+max)?", txt)
