@@ -201,14 +201,18 @@ int mmx_image_stats(mmx_sim* sim, const uint8_t* rgb_dev, int64_t img_stride, in
 
 /* Physics-level entry points (parity harnesses): n x mujoco.mj_step with the current ctrl
  * (env.py:119-121), optionally preceded by IKController.compute toward the decoded target
- * each substep; and the mj_forward position stage (kinematics + IK cache). */
+ * each substep; and the mj_forward position stage (kinematics + IK cache).  mmx_physics_step
+ * runs one launch per substep of the one-substep kernel of the sim's step layout (mmx_step_rows,
+ * mmx_tuning.h): the 128-row single-wave kernel, or the 192-row kernel with its helper wave, so a
+ * harness checks the very code (row build, solver, overflow rows) that mmx_step runs at that layout. */
 int mmx_physics_step(mmx_sim* sim, int32_t n, int32_t with_ik);
 int mmx_forward(mmx_sim* sim);
 
 /* Per-physics-step expert loop (main.py:65-91; tests/test_pick_and_place.py:147-166):
  * n x (PickAndPlaceTask.update() = plan(1) + _actuate() (pick_and_place.py:279-304) ;
  * mujoco.mj_step), the FSM reading data.xpos as the previous mj_step left it.  No gym
- * bookkeeping (no reward, observation or autoreset); the FSM state is in episode_i. */
+ * bookkeeping (no reward, observation or autoreset); the FSM state is in episode_i.  This loop
+ * exists in the 128-row layout only, whatever mmx_step_rows says. */
 int mmx_expert_physics(mmx_sim* sim, int32_t n_physics_steps);
 
 /* Reward-layer parity harness (gym_env.py:341-470, 562-573).  For every env: the object at

@@ -29,6 +29,7 @@ extern "C" hipError_t mmx_launch_traj_l192(const MMXState* S, const MMXTraj* R, 
 extern "C" hipError_t mmx_launch_order(const MMXState* S, int base, int count, int* order, int threads, hipStream_t st);
 extern "C" hipError_t mmx_launch_expert(const MMXState* S, int n, float* action, hipStream_t st);
 extern "C" hipError_t mmx_launch_physics(const MMXState* S, int n, int with_ik, hipStream_t st);
+extern "C" hipError_t mmx_launch_physics_l192(const MMXState* S, int n, int with_ik, hipStream_t st);
 extern "C" hipError_t mmx_launch_forward(const MMXState* S, hipStream_t st);
 extern "C" hipError_t mmx_launch_render(const MMXState* S, int base, int count, hipStream_t st);
 extern "C" hipError_t mmx_launch_render_bg(const MMXState* S, hipStream_t st);
@@ -490,14 +491,15 @@ int mmx_reset(mmx_sim* sim, const uint64_t* seeds, const uint8_t* seed_given, co
 
 namespace {
 // the step kernels' launchers of the sim's LDS-row layout (mmx_step.inc is built at 128 and at 192 rows):
-// the one place the layout is chosen, for mmx_step and the rollouts
+// the one place the layout is chosen, for mmx_step, the rollouts and mmx_physics_step
 struct StepLaunchers {
   decltype(&mmx_launch_step) step;
   decltype(&mmx_launch_traj) traj;
+  decltype(&mmx_launch_physics) physics;
 };
 StepLaunchers step_launchers(const mmx_sim* sim) {
-  return sim->step_rows == 192 ? StepLaunchers{mmx_launch_step_l192, mmx_launch_traj_l192}
-                               : StepLaunchers{mmx_launch_step, mmx_launch_traj};
+  return sim->step_rows == 192 ? StepLaunchers{mmx_launch_step_l192, mmx_launch_traj_l192, mmx_launch_physics_l192}
+                               : StepLaunchers{mmx_launch_step, mmx_launch_traj, mmx_launch_physics};
 }
 // floats per env that each action mode's action needs
 constexpr int kDim[5] = {4, 8, 10, 8, 10};
@@ -818,7 +820,7 @@ int mmx_rollout_steps_per_launch(const mmx_sim* sim) {
 int mmx_physics_step(mmx_sim* sim, int32_t n, int32_t with_ik) {
   if (!sim || n < 0) return MMX_EINVAL;
   DeviceGuard guard(sim);
-  return hip_check(sim, mmx_launch_physics(&sim->S, n, with_ik, sim->stream), "mmx_physics_step");
+  return hip_check(sim, step_launchers(sim).physics(&sim->S, n, with_ik, sim->stream), "mmx_physics_step");
 }
 
 int mmx_expert_physics(mmx_sim* sim, int32_t n) {

@@ -1,45 +1,9 @@
-// The 128-row step kernels (mmx_step.inc at its default layout: twelve envs per CU) and every kernel
-// that exists once, whatever the layout: one substep per launch (the physics harnesses), forward,
-// reset, the expert's loops, the reward harness, the episode queue and the dispatch order, with their
-// launchers.  They use the 128-row LDS record of the include; mmx_step_l192.hip builds the step
-// kernels alone a second time at 192 rows.
+// The 128-row step kernels (mmx_step.inc at its default layout: twelve envs per CU; with them the
+// one-substep kernel of the physics harness) and every kernel that exists once, whatever the layout:
+// forward, reset, the expert's loops, the reward harness, the episode queue and the dispatch order, with
+// their launchers.  They use the 128-row LDS record of the include; mmx_step_l192.hip builds the step
+// kernels and the one-substep kernel a second time at 192 rows.
 #include "mmx_step.inc"
-
-// One IK + mj_step substep per launch (mmx_launch_physics; with SS_GYM the env step's first / last)
-extern "C" __global__ void __launch_bounds__(WG) mmx_substep_kernel(MMXState S, const float* action, int adim, int mode) {
-  EnvSh& E = g_E;
-  float* act = scr_of(E) + SCR_ACT;  // lane 0's decoded action (E.J is free before the substeps)
-  const int i = blockIdx.x;
-  if (i >= S.N) return;
-  load_env(S, i, E);
-  if ((mode & SS_FIRST) && (mode & SS_GYM) && LANE == 0) {
-    if (mode & SS_EXPERT) expert_plan(S, i, obj_pos(E, EPI(EPI_OBJ)), hand_pos(E), MMX_NSUBSTEP, act);
-    else
-      for (int k = 0; k < adim && k < 12; k++) act[k] = action[(size_t)i * adim + k];
-    decode_lane0(S, i, E, act);
-  }
-  SYNC();
-  {
-    float* stats = E.stats;
-    CLK_DECL;
-    if (mode & SS_IK) ik_wave(E);  // IK on the kinematics of the previous position stage
-    SYNC();
-    CLK(stats, STAT_T_IK);
-  }
-  mj_step_wave(S.solver_max_iter, S.solver_tol, E, (mode & SS_LAST) ? contacts_dst(S, i) : nullptr);
-  if ((mode & SS_LAST) && (mode & SS_GYM)) {
-    step_end(S, i, E);
-  } else {
-    if (LANE == 0) {
-      fold_flags(S, i, E);
-      if (mode & SS_LAST) {
-        EPI(EPI_NCON) = E.ncon;
-        EPI(EPI_NEFC) = E.nefc_mj;
-      }
-    }
-  }
-  store_env(S, i, E);
-}
 
 // mj_forward position stage only (kinematics -> IK cache) + observation refresh
 extern "C" __global__ void __launch_bounds__(WG) mmx_forward_kernel(MMXState S) {
@@ -266,13 +230,6 @@ extern "C" hipError_t mmx_launch_reset(const MMXState* S, const unsigned char* m
 }
 extern "C" hipError_t mmx_launch_expert(const MMXState* S, int n, float* action, hipStream_t st) {
   hipLaunchKernelGGL(mmx_expert_kernel, dim3((S->N + WG - 1) / WG), dim3(WG), 0, st, *S, n, action);
-  return hipGetLastError();
-}
-extern "C" hipError_t mmx_launch_physics(const MMXState* S, int n, int with_ik, hipStream_t st) {
-  for (int sub = 0; sub < n; sub++) {
-    const int mode = (with_ik ? SS_IK : 0) | (sub == n - 1 ? SS_LAST : 0);
-    hipLaunchKernelGGL(mmx_substep_kernel, dim3(S->N), dim3(WG), 0, st, *S, nullptr, 0, mode);
-  }
   return hipGetLastError();
 }
 extern "C" hipError_t mmx_launch_expert_physics(const MMXState* S, int n, hipStream_t st) {

@@ -17,9 +17,10 @@
 // Physics follows MuJoCo's documented pipeline (the fp64 oracle in oracle/ is the checker).
 //
 // This file is everything that is compiled once per LDS-row layout: the LDS record (EnvSh), the phases,
-// substep / step_begin / step_finish, the two step kernels and their launchers.  It is included, never
+// substep / step_begin / step_finish, the two step kernels, the one-substep kernel of the physics harness
+// and their launchers.  It is included, never
 // compiled on its own: by mmx_kernels.hip at the default MMX_LDSEFC = 128, which adds the kernels that
-// exist once (substep, forward, reset, expert, reward, queue, order), and by mmx_step_l192.hip at 192
+// exist once (forward, reset, expert, reward, queue, order), and by mmx_step_l192.hip at 192
 // rows with MMX_STEP_SUFFIX _l192 on the kernels' and launchers' names (MMX_STEP_SYM).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -3454,6 +3455,66 @@ MMX_NO_TAIL_MARK MMX_STEP_SYM(mmx_env_traj_kernel)(MMXState S, MMXTraj R, const 
   }
 }
 
+// One IK + mj_step substep per launch (mmx_launch_physics, the physics-level harness of mmx_physics_step;
+// with SS_GYM the env step's first / last), in the build's own layout like the step kernels above.  With
+// the helper wave (192 rows), threads 64..127 run one substep of mmx_env_step_kernel's helper loop: the
+// barrier after the record load, then mj_step_wave's C, K, A, P, Q in that order.  The IK runs only with
+// SS_IK; its two barriers C and K are crossed either way, and no path of either wave skips one.
+extern "C" __global__ void __launch_bounds__(MMX_STEP_THREADS) MMX_STEP_SYM(mmx_substep_kernel)(MMXState S, const float* action,
+                                                                                            int adim, int mode) {
+  EnvSh& E = g_E;
+  float* act = scr_of(E) + SCR_ACT;  // lane 0's decoded action (E.J is free before the substeps)
+  const int i = blockIdx.x;
+  if (i >= S.N) return;
+#if MMX_STEP_HELPER
+  if (threadIdx.x >= 64) {  // the helper wave: the same workgroup barriers as the env's wave below
+    XSYNC();                // the record load
+    __syncthreads();        // C
+    if (mode & SS_IK) ik_wave(E);
+    __syncthreads();  // K: the IK has read the kinematics cache; the env wave may overwrite it
+    __syncthreads();  // A
+    dynamics_wave(E);
+    __syncthreads();  // P
+    collide_pairs(E, false, 2);
+    __syncthreads();  // Q
+    return;
+  }
+#endif
+  load_env(S, i, E);
+  if ((mode & SS_FIRST) && (mode & SS_GYM) && LANE == 0) {
+    if (mode & SS_EXPERT) expert_plan(S, i, obj_pos(E, EPI(EPI_OBJ)), hand_pos(E), MMX_NSUBSTEP, act);
+    else
+      for (int k = 0; k < adim && k < 12; k++) act[k] = action[(size_t)i * adim + k];
+    decode_lane0(S, i, E, act);
+  }
+  SYNC();
+#if MMX_STEP_HELPER
+  XSYNC();  // the record and the decoded target are in LDS (the helper's IK and dynamics read them)
+#endif
+  {
+    float* stats = E.stats;
+    CLK_DECL;
+#if !MMX_STEP_HELPER  // (the helper wave's, beside the kinematics: mj_step_wave)
+    if (mode & SS_IK) ik_wave(E);  // IK on the kinematics of the previous position stage
+    SYNC();
+#endif
+    CLK(stats, STAT_T_IK);
+  }
+  mj_step_wave(S.solver_max_iter, S.solver_tol, E, (mode & SS_LAST) ? contacts_dst(S, i) : nullptr);
+  if ((mode & SS_LAST) && (mode & SS_GYM)) {
+    step_end(S, i, E);
+  } else {
+    if (LANE == 0) {
+      fold_flags(S, i, E);
+      if (mode & SS_LAST) {
+        EPI(EPI_NCON) = E.ncon;
+        EPI(EPI_NEFC) = E.nefc_mj;
+      }
+    }
+  }
+  store_env(S, i, E);
+}
+
 // ===================================================================== the step kernels' launchers
 // Occupancy probe (diagnostics only, never set by the product): MMX_LDS_PAD bytes of dynamic LDS
 // per step-kernel workgroup lower the envs per CU (tools/occupancy_probe.sh).
@@ -3471,6 +3532,14 @@ extern "C" hipError_t MMX_STEP_SYM(mmx_launch_step)(const MMXState* S, const flo
   if (nsteps > 1 && !expert) return hipErrorInvalidValue;  // host actions: one env step per launch
   hipLaunchKernelGGL(MMX_STEP_SYM(mmx_env_step_kernel), dim3(count), dim3(MMX_STEP_THREADS), step_lds_pad(), st, *S, action, adim, expert, base,
                      nsteps, order);
+  return hipGetLastError();
+}
+// n substeps of every env, one launch each (mmx_physics_step)
+extern "C" hipError_t MMX_STEP_SYM(mmx_launch_physics)(const MMXState* S, int n, int with_ik, hipStream_t st) {
+  for (int sub = 0; sub < n; sub++) {
+    const int mode = (with_ik ? SS_IK : 0) | (sub == n - 1 ? SS_LAST : 0);
+    hipLaunchKernelGGL(MMX_STEP_SYM(mmx_substep_kernel), dim3(S->N), dim3(MMX_STEP_THREADS), 0, st, *S, nullptr, 0, mode);
+  }
   return hipGetLastError();
 }
 // `nsteps` env steps of envs [base, base+count) from the rollout's step k0 on, with per-step actions and record

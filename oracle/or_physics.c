@@ -700,6 +700,31 @@ int or_get_efc(or_env* e, int* type, double* pos, double* R, double* aref) {
   }
   return e->nefc;
 }
+/* Cost, gradient (grad[NV], may be NULL) and the solver's relative residual |g| / (1 + |qfrc_smooth|) of
+ * the last forward's constraint problem at a given acceleration x: how well another solver's solution
+ * solves this one's problem. */
+double or_eval_cost(or_env* e, const double* x, double* grad, double* rel_residual) {
+  double g[NV], dx[NV];
+  for (int i = 0; i < NV; i++) dx[i] = x[i] - e->qacc_smooth[i];
+  Mmul(e, dx, g);
+  for (int k = 0; k < e->nefc; k++) {
+    double v = -e->efc_aref[k];
+    for (int d = 0; d < NV; d++) v += e->efc_J[k][d] * x[d];
+    if (e->efc_type[k] == EFC_EQUALITY || v < 0)
+      for (int d = 0; d < NV; d++) g[d] += e->efc_D[k] * v * e->efc_J[k][d];
+  }
+  double gn = 0, sc = 0;
+  for (int d = 0; d < NV; d++) {
+    gn += g[d] * g[d];
+    sc += e->qfrc_smooth[d] * e->qfrc_smooth[d];
+  }
+  if (grad) memcpy(grad, g, sizeof(g));
+  if (rel_residual) *rel_residual = sqrt(gn) / (1 + sqrt(sc));
+  return cost_at(e, x);
+}
+void or_get_efc_J(or_env* e, double* J) {
+  for (int k = 0; k < e->nefc; k++) memcpy(J + (size_t)k * NV, e->efc_J[k], NV * sizeof(double));
+}
 void or_get_qacc(or_env* e, double* qacc) { memcpy(qacc, e->qacc, sizeof(e->qacc)); }
 void or_get_mass_matrix(or_env* e, double* M) { memcpy(M, e->M, sizeof(e->M)); }
 /* the smooth-force terms of the last forward (tests/test_smooth_dynamics_kat.py pins them against

@@ -127,6 +127,20 @@ int main(int argc, char** argv) {
         or_mj_step(e);
         total++;
       }
+      /* the cost hook at the solver's own solution of the last forward: a converged residual, a minimum */
+      {
+        static double J[OR_MAXEFC * NV];
+        double x[NV], g[NV], res = -1;
+        or_get_qacc(e, x);
+        or_get_efc_J(e, J);
+        const double c = or_eval_cost(e, x, g, &res);
+        if (!isfinite(c) || !(res >= 0 && res < 1e-6)) {
+          fprintf(stderr, "or_eval_cost: cost %g residual %g, the solver's %g\n", c, res, or_solver_residual(e));
+          return 2;
+        }
+        for (int i = 0; i < NV; i++) x[i] += 1.0;
+        if (!(or_eval_cost(e, x, NULL, NULL) > c)) { fprintf(stderr, "or_eval_cost: no minimum at qacc\n"); return 2; }
+      }
       or_get_state(e, qpos, qvel, ctrl, ws);
       for (int i = 0; i < NQ; i++)
         if (!isfinite(qpos[i])) { fprintf(stderr, "non-finite qpos after pile %d\n", trial); return 2; }

@@ -82,7 +82,11 @@ void or_solver_stats(or_env* e, long* calls, long* iters);
 /* constraint rows of the last solve: type (0 equality, 1 limit, 2 contact edge), pos, R, aref;
  * returns nefc (NULL skips a field; arrays hold OR_MAXEFC) */
 int or_get_efc(or_env* e, int* type, double* pos, double* R, double* aref);
+void or_get_efc_J(or_env* e, double* J); /* the rows' Jacobians [nefc][nv] of the last solve */
 void or_get_qacc(or_env* e, double* qacc);
+/* cost of the last forward's constraint problem at acceleration x[nv]; its gradient into grad[nv] and
+ * the solver's relative residual |grad| / (1 + |qfrc_smooth|) into *rel_residual (either may be NULL) */
+double or_eval_cost(or_env* e, const double* x, double* grad, double* rel_residual);
 void or_get_mass_matrix(or_env* e, double* M); /* qM (dense NV x NV, CRBA + armature) of the last forward */
 void or_get_smooth(or_env* e, double* bias, double* act, double* passive, double* qacc_smooth, double* constraint,
                    double* act_force); /* smooth-force terms of the last forward */

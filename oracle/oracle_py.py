@@ -68,6 +68,9 @@ def lib():
         L.or_solver_residual.restype = C.c_double
         L.or_solver_residual.argtypes = [C.c_void_p]
         L.or_get_qacc.argtypes = [C.c_void_p, dp]
+        L.or_get_efc_J.argtypes = [C.c_void_p, dp]
+        L.or_eval_cost.restype = C.c_double
+        L.or_eval_cost.argtypes = [C.c_void_p, dp, dp, dp]
         L.or_set_solver.argtypes = [C.c_void_p, C.c_double, C.c_int]
         L.or_set_solver_mj.argtypes = [C.c_void_p, C.c_double]
         L.or_solver_stats.argtypes = [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long)]
@@ -306,6 +309,19 @@ class OracleEnv:
         q = np.zeros(NV)
         lib().or_get_qacc(self.ptr, _d(q))
         return q
+
+    def efc_J(self):
+        """The rows' Jacobians [nefc, NV] of the last solve."""
+        J = np.zeros((max(1, self.nefc()), NV))
+        lib().or_get_efc_J(self.ptr, _d(J))
+        return J[:self.nefc()]
+
+    def eval_cost(self, x):
+        """(cost, gradient [NV], relative residual) of the last forward's constraint problem at the
+        acceleration x: the residual is the solver's own convergence measure, |g| / (1 + |qfrc_smooth|)."""
+        g, res = np.zeros(NV), C.c_double()
+        c = lib().or_eval_cost(self.ptr, _d(np.ascontiguousarray(x, float)), _d(g), C.byref(res))
+        return c, g, res.value
 
     def mass_matrix(self):
         """qM of the last forward (CRBA + armature), dense NV x NV."""

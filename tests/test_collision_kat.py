@@ -390,8 +390,8 @@ def test_oracle_mesh_scenes(raw):
 
 
 # --------------------------------------------------------------------------- GPU (HIP kernel)
-def gpu_contacts(qs):
-    """Contacts of one substep of the kernel from each state (one env per state)."""
+def gpu_contacts(qs, rows):
+    """Contacts of one substep of the kernel from each state (one env per state), on the given step layout."""
     import torch
 
     from mujoco_manip_amd import _lib
@@ -401,6 +401,8 @@ def gpu_contacts(qs):
     n = len(qs)
     sim = _lib.Sim(n, action_mode="abs_pos", image_size=0)
     sim.reset()
+    sim.step_rows = rows
+    assert sim.step_rows == rows
     _, _, ctrl, _ = sim.get_state()
     Q = np.asarray(qs, np.float32)
     sim.set_state(Q, np.zeros((n, 27), np.float32), ctrl, np.zeros((n, 27), np.float32))
@@ -416,34 +418,64 @@ def gpu_contacts(qs):
     return out, Q.astype(np.float64)
 
 
-@pytest.mark.gpu
-def test_gpu_box_scenes(raw):
+def _test_gpu_box_scenes(raw, rows):
     ids = compiled_ids(raw)
     scenes = [f(raw) for f in BOX_SCENES]
-    got, _ = gpu_contacts([q for q, _ in scenes])
+    got, _ = gpu_contacts([q for q, _ in scenes], rows)
     for (q, wants), con, f in zip(scenes, got, BOX_SCENES):
         for w in wants:
             check(raw, ids, con, w, GPU_TOL_CONVEX if w.get("convex") else GPU_TOL_BOX, f.__name__)
 
 
-@pytest.mark.gpu
-def test_gpu_cube_pair_scenes(raw):
+def _test_gpu_cube_pair_scenes(raw, rows):
     """The cube-on-cube scenes with the pairs (red, blue) and (green, blue): the box-box narrowphase
     and the pair order do not depend on which two cubes touch."""
     ids = compiled_ids(raw)
     scenes = [(f, lo, up, f(raw, lo, up)) for lo, up in CUBE_PAIRS for f in CUBE_SCENES]
-    got, _ = gpu_contacts([q for _, _, _, (q, _) in scenes])
+    got, _ = gpu_contacts([q for _, _, _, (q, _) in scenes], rows)
     for (f, lo, up, (q, wants)), con in zip(scenes, got):
         for w in wants:
             check(raw, ids, con, w, GPU_TOL_BOX, f"{f.__name__}({lo}, {up})")
 
 
-@pytest.mark.gpu
-def test_gpu_mesh_scenes(raw):
+def _test_gpu_mesh_scenes(raw, rows):
     """GJK / EPA on the kernel against the exact penetration of the raw-asset hulls, answers
     recomputed at the fp32-rounded states the kernel actually ran."""
     ids = compiled_ids(raw)
     scenes = mesh_scenes(raw)
-    got, Q = gpu_contacts([q for _, q in scenes])
+    got, Q = gpu_contacts([q for _, q in scenes], rows)
     for (s, _), con, q32 in zip(scenes, got, Q):
         check(raw, ids, con, mesh_answer(raw, s, q32), GPU_TOL_CONVEX, f"{s['kind']}:{s['mesh']}")
+
+
+# Each physics-level test on both step layouts: physics_step runs the one-substep kernel of the sim's layout.
+# The test of the 128-row single-wave kernel keeps its name; _l192 is the 192-row kernel with its helper wave.
+
+@pytest.mark.gpu
+def test_gpu_box_scenes(raw):
+    _test_gpu_box_scenes(rows=128, raw=raw)
+
+
+@pytest.mark.gpu
+def test_gpu_box_scenes_l192(raw):
+    _test_gpu_box_scenes(rows=192, raw=raw)
+
+
+@pytest.mark.gpu
+def test_gpu_cube_pair_scenes(raw):
+    _test_gpu_cube_pair_scenes(rows=128, raw=raw)
+
+
+@pytest.mark.gpu
+def test_gpu_cube_pair_scenes_l192(raw):
+    _test_gpu_cube_pair_scenes(rows=192, raw=raw)
+
+
+@pytest.mark.gpu
+def test_gpu_mesh_scenes(raw):
+    _test_gpu_mesh_scenes(rows=128, raw=raw)
+
+
+@pytest.mark.gpu
+def test_gpu_mesh_scenes_l192(raw):
+    _test_gpu_mesh_scenes(rows=192, raw=raw)

@@ -401,13 +401,13 @@ def _gpu_parity_run(rows, nsub):
         sim = _sim(len(scenes), rows)
         _set(sim, [st for _, st, _ in scenes])
         sim.physics_step(nsub, with_ik=False)
-        q, v, _, _ = sim.get_state()
+        q, v, _, w = sim.get_state()
         cons, ncon, raw = _record(sim)
         stats = sim.view("stats", _lib.STAT_N)[:, :2].cpu().numpy().copy()
         solve = _solver_stats(sim)
         err = _errors(sim).copy()
         sim.close()
-        _GPU[("parity", rows, nsub)] = dict(q=q, v=v, cons=cons, ncon=ncon, raw=raw, stats=stats, err=err, solve=solve)
+        _GPU[("parity", rows, nsub)] = dict(q=q, v=v, w=w, cons=cons, ncon=ncon, raw=raw, stats=stats, err=err, solve=solve)
     return _GPU[("parity", rows, nsub)]
 
 
@@ -453,13 +453,17 @@ def test_gpu_coupled_parity(rows, nsub, tol_q, tol_v, margin):
 @pytest.mark.gpu
 @pytest.mark.parametrize("nsub", [1, 16])
 def test_gpu_coupled_layouts_agree(nsub, margin):
-    """The 128-row and 192-row layouts give bit-identical results on the coupled states: qpos, qvel
-    and the contact record (test_step_layouts_agree's claim, extended to the general solve)."""
+    """The 128-row and 192-row layouts give bit-identical results on the coupled states: qpos, qvel,
+    the solver's solution (qacc_warmstart) and the contact record (test_step_layouts_agree's claim,
+    extended to the general solve).  physics_step runs the one-substep kernel of the sim's layout
+    (mmx_physics_step), so the two runs are the single-wave 128-row kernel and the 192-row kernel
+    with its helper wave."""
     a, b = _gpu_parity_run(128, nsub), _gpu_parity_run(192, nsub)
-    d = max(float(np.abs(a["q"] - b["q"]).max()), float(np.abs(a["v"] - b["v"]).max()))
+    d = max(float(np.abs(a[k] - b[k]).max()) for k in ("q", "v", "w"))
     margin("max_abs_dstate", d, 0.0)
     np.testing.assert_array_equal(a["q"], b["q"])
     np.testing.assert_array_equal(a["v"], b["v"])
+    np.testing.assert_array_equal(a["w"], b["w"])
     np.testing.assert_array_equal(a["ncon"], b["ncon"])
     np.testing.assert_array_equal(a["raw"], b["raw"])
 

@@ -33,9 +33,14 @@ def gpu():
 TARGET_ORI = np.array([[0, 1, 0], [1, 0, 0], [0, 0, -1.0]])
 
 
+_SHARED = {}  # oracle references and the pile states: computed once, shared by the layouts' cases, never modified
+
+
 def oracle_states(n=40):
     import oracle_py as O
 
+    if ("fsm_states", n) in _SHARED:
+        return _SHARED[("fsm_states", n)]
     e = O.OracleEnv()
     e.reset_keyframe()
     e.fsm_init([(0, 0)])
@@ -49,28 +54,37 @@ def oracle_states(n=40):
         if st == 10:
             break
     idx = np.linspace(0, len(states) - 1, n).astype(int)
-    return [states[i] for i in idx]
+    _SHARED[("fsm_states", n)] = [states[i] for i in idx]
+    return _SHARED[("fsm_states", n)]
 
 
-def _physics_parity(nsub, sts=None, nefc_out=None):
+def _physics_parity(nsub, rows, sts=None, nefc_out=None, tag="fsm"):
+    """physics_step(nsub) of the `rows` layout's one-substep kernel against the oracle, from the states `sts`
+    (`tag` names them: the oracle's results are kept per (tag, nsub))."""
     import oracle_py as O
     from mujoco_manip_amd import _lib
 
     sts = oracle_states() if sts is None else sts
     qpos, qvel, ctrl, ws = [np.stack([s[k] for s in sts]).astype(np.float32) for k in range(4)]
     sim = _lib.Sim(len(sts))
+    sim.step_rows = rows
+    assert sim.step_rows == rows
     sim.set_state(qpos, qvel, ctrl, ws)
     sim.physics_step(nsub)
     gq, gv, _, _ = sim.get_state()
     if nefc_out is not None:  # constraint rows of the run (summed over its substeps), per env
         nefc_out.append(sim.view("stats", _lib.STAT_N)[:, 0].cpu().numpy().copy())
+    if ("oracle", tag, nsub) not in _SHARED:
+        ref = []
+        for k in range(len(sts)):
+            e = O.OracleEnv()
+            e.set_state(*(a[k].astype(float) for a in (qpos, qvel, ctrl, ws)))
+            for _ in range(nsub):
+                e.mj_step()
+            ref.append(e.get_state()[:2])
+        _SHARED[("oracle", tag, nsub)] = ref
     err_q, err_v = [], []
-    for k in range(len(sts)):
-        e = O.OracleEnv()
-        e.set_state(*(a[k].astype(float) for a in (qpos, qvel, ctrl, ws)))
-        for _ in range(nsub):
-            e.mj_step()
-        rq, rv, _, _ = e.get_state()
+    for k, (rq, rv) in enumerate(_SHARED[("oracle", tag, nsub)]):
         err_q.append(np.abs(gq[k] - rq).max())
         err_v.append(np.abs(gv[k] - rv).max())
     errs = sim.view("episode_i", _lib.EPI_N, "<i4")[:, 9].cpu().numpy()
@@ -78,8 +92,8 @@ def _physics_parity(nsub, sts=None, nefc_out=None):
     return np.array(err_q), np.array(err_v)
 
 
-def test_physics_parity_one_substep(margin):  # L1: fp32 GPU vs fp64 oracle, contacts incl. grasps
-    dq, dv = _physics_parity(1)
+def _test_physics_parity_one_substep(rows, margin):  # L1: fp32 GPU vs fp64 oracle, contacts incl. grasps
+    dq, dv = _physics_parity(1, rows)
     margin("max_abs_dqpos", float(dq.max()), 1e-5)
     margin("max_abs_dqvel", float(dv.max()), 5e-3)
     assert dq.max() < 1e-5, dq.max()
@@ -189,8 +203,8 @@ def test_step_layouts_agree(margin):
     assert dmax == 0.0 and fsm_diff == 0, (dmax, first_diff, fsm_diff)
 
 
-def test_physics_parity_one_env_step(margin):  # L1: 16 substeps; SURVEY bound qpos <= 1e-4
-    dq, dv = _physics_parity(16)
+def _test_physics_parity_one_env_step(rows, margin):  # L1: 16 substeps; SURVEY bound qpos <= 1e-4
+    dq, dv = _physics_parity(16, rows)
     margin("max_abs_dqpos", float(dq.max()), 1e-4)
     margin("max_abs_dqvel", float(dv.max()), 2e-2)
     assert dq.max() < 1e-4, dq.max()
@@ -205,6 +219,8 @@ def _pile_states(n_want=6, min_mean_nefc=215.0):
 
     import oracle_py as O
 
+    if ("pile", n_want, min_mean_nefc) in _SHARED:
+        return _SHARED[("pile", n_want, min_mean_nefc)]
     env = PickPlaceVecEnv(1024, tasks="all", action_mode="abs_pos", reward_type="staged", randomize_objects=True,
                           autoreset=True, image_size=0)
     env.reset(seed=[O.episode_seed(42, i) for i in range(1024)])
@@ -219,14 +235,15 @@ def _pile_states(n_want=6, min_mean_nefc=215.0):
         if len(found) >= n_want:
             break
     env.close()
+    _SHARED[("pile", n_want, min_mean_nefc)] = found[:n_want]
     return found[:n_want]
 
 
-def test_physics_parity_hbm_overflow_rows(margin):  # L1 on contact piles: rows 128..303 live in HBM
+def _test_physics_parity_hbm_overflow_rows(rows, margin):  # L1 on contact piles: rows 128..303 live in HBM
     sts = _pile_states()
     assert len(sts) >= 4, f"only {len(sts)} pile states in 400 C3 steps"
     rows1, rows16 = [], []
-    dq, dv = _physics_parity(1, sts, rows1)
+    dq, dv = _physics_parity(1, rows, sts, rows1, tag="pile")
     print(f"pile states: rows of the first substep {rows1[0].astype(int).tolist()}, errors qpos {dq.max():.2e} "
           f"qvel {dv.max():.2e}")
     assert (rows1[0] > 192).any(), f"no substep used the overflow rows deeply: {rows1[0]}"
@@ -234,7 +251,7 @@ def test_physics_parity_hbm_overflow_rows(margin):  # L1 on contact piles: rows 
     margin("substep1_max_abs_dqvel", float(dv.max()), 5e-3)
     assert dq.max() < 1e-5, dq.max()
     assert dv.max() < 5e-3, dv.max()
-    dq, dv = _physics_parity(16, sts, rows16)
+    dq, dv = _physics_parity(16, rows, sts, rows16, tag="pile")
     margin("substep16_max_abs_dqpos", float(dq.max()), 1e-4)
     margin("substep16_max_abs_dqvel", float(dv.max()), 2e-2)
     assert dq.max() < 1e-4, dq.max()
@@ -586,3 +603,30 @@ def test_sampling_exhaustion_on_autoreset_reported_at_sync():
         env.synchronize()
     assert ((env.env_error.cpu().numpy() & _lib.ERR_SAMPLING) != 0).all()
     assert np.isfinite(env.qpos.cpu().numpy()).all()
+
+
+# Each physics-level test on both step layouts: physics_step runs the one-substep kernel of the sim's layout.
+# The test of the 128-row single-wave kernel keeps its name; _l192 is the 192-row kernel with its helper wave.
+
+def test_physics_parity_one_substep(margin):
+    _test_physics_parity_one_substep(rows=128, margin=margin)
+
+
+def test_physics_parity_one_substep_l192(margin):
+    _test_physics_parity_one_substep(rows=192, margin=margin)
+
+
+def test_physics_parity_one_env_step(margin):
+    _test_physics_parity_one_env_step(rows=128, margin=margin)
+
+
+def test_physics_parity_one_env_step_l192(margin):
+    _test_physics_parity_one_env_step(rows=192, margin=margin)
+
+
+def test_physics_parity_hbm_overflow_rows(margin):
+    _test_physics_parity_hbm_overflow_rows(rows=128, margin=margin)
+
+
+def test_physics_parity_hbm_overflow_rows_l192(margin):
+    _test_physics_parity_hbm_overflow_rows(rows=192, margin=margin)

@@ -349,15 +349,20 @@ def _oracle_states(n=40):
     return [states[i] for i in idx], [targets[i] for i in idx]
 
 
-def _ik_parity(states, targets, nsub):
-    """GPU: physics_step(nsub, with_ik) toward `targets`; oracle: nsub x (IKController.compute ->
-    set_arm_ctrl -> mj_step), both from a consistent position stage (mj_forward)."""
+_IK_REF = {}  # the oracle's results per (tag, nsub): computed once, shared by the layouts' cases
+
+
+def _ik_parity(states, targets, nsub, rows, tag):
+    """GPU: physics_step(nsub, with_ik) of the `rows` layout's one-substep kernel toward `targets`; oracle:
+    nsub x (IKController.compute -> set_arm_ctrl -> mj_step), both from a consistent position stage (mj_forward)."""
     import oracle_py as O
     from mujoco_manip_amd import _lib
 
     qpos, qvel, ctrl, ws = [np.stack([s[k] for s in states]).astype(np.float32) for k in range(4)]
     n = len(states)
     sim = _lib.Sim(n, action_mode="abs_pos", image_size=0)
+    sim.step_rows = rows
+    assert sim.step_rows == rows
     sim.set_state(qpos, qvel, ctrl, ws)
     sim.forward()
     tgt = sim.view("target", 4)
@@ -368,36 +373,42 @@ def _ik_parity(states, targets, nsub):
     errs = sim.view("episode_i", _lib.EPI_N, "<i4")[:, 9].cpu().numpy()
     sim.close()
     assert (errs == 0).all()
+    if (tag, nsub) not in _IK_REF:
+        ref = []
+        for k in range(n):
+            e = O.OracleEnv()
+            e.set_state(*(a[k].astype(float) for a in (qpos, qvel, ctrl, ws)))
+            e.mj_forward()
+            for _ in range(nsub):
+                e.set_arm_ctrl(e.ik(np.asarray(targets[k], float)))
+                e.mj_step()
+            ref.append(e.get_state()[:3])
+        _IK_REF[(tag, nsub)] = ref
     out = []
-    for k in range(n):
-        e = O.OracleEnv()
-        e.set_state(*(a[k].astype(float) for a in (qpos, qvel, ctrl, ws)))
-        e.mj_forward()
-        for _ in range(nsub):
-            e.set_arm_ctrl(e.ik(np.asarray(targets[k], float)))
-            e.mj_step()
-        rq, rv, rc, _ = e.get_state()
+    for k, (rq, rv, rc) in enumerate(_IK_REF[(tag, nsub)]):
         out.append((np.abs(gq[k] - rq).max(), np.abs(gv[k] - rv).max(), np.abs(gc[k, :7] - rc[:7]).max()))
     return np.array(out)
 
 
-def test_physics_parity_with_ik_from_oracle_states(margin):
+def _test_physics_parity_with_ik_from_oracle_states(rows, margin):
     """L1 with the IK in the loop (SURVEY A.5 stale kinematics at substeps >= 1): 40 states along an
     oracle expert episode incl. grasps and contacts, toward the FSM's own targets."""
-    states, targets = _oracle_states()
-    e1 = _ik_parity(states, targets, 1)
+    if "fsm_states" not in _IK_REF:
+        _IK_REF["fsm_states"] = _oracle_states()
+    states, targets = _IK_REF["fsm_states"]
+    e1 = _ik_parity(states, targets, 1, rows, "fsm")
     margin("substep1_ctrl", float(e1[:, 2].max()), 2e-5)
     margin("substep1_dqpos", float(e1[:, 0].max()), 1e-5)
     margin("substep1_dqvel", float(e1[:, 1].max()), 5e-3)
     assert e1[:, 2].max() < 2e-5, e1[:, 2].max()  # IK output (ctrl[:7]) after one compute
     assert e1[:, 0].max() < 1e-5 and e1[:, 1].max() < 5e-3, e1.max(0)
-    e16 = _ik_parity(states, targets, 16)
+    e16 = _ik_parity(states, targets, 16, rows, "fsm")
     margin("substep16_dqpos", float(e16[:, 0].max()), 1e-4)
     margin("substep16_dqvel", float(e16[:, 1].max()), 2e-2)
     assert e16[:, 0].max() < 1e-4 and e16[:, 1].max() < 2e-2, e16.max(0)
 
 
-def test_ik_edge_states(margin):
+def _test_ik_edge_states(rows, margin):
     """IKController.compute edge cases (controller.py:21-43, 125-135) on device vs the oracle: the
     ||dq|| > 5 clamp (far targets), the joint-range clip (joints at / past their limits) and a hand
     rotated ~pi about its axis from TARGET_ORI (orientation error near pi)."""
@@ -424,7 +435,7 @@ def test_ik_edge_states(margin):
     e.set_state(q0, v0, c0, w0)
     e.mj_forward()
     assert np.linalg.norm(e.ik(targets[0]) - q0[:7]) > 1.0
-    err = _ik_parity(states, targets, 1)
+    err = _ik_parity(states, targets, 1, rows, "edge")
     margin("ctrl", float(err[:, 2].max()), 5e-5)
     margin("dqpos", float(err[:, 0].max()), 1e-5)
     assert err[:, 2].max() < 5e-5, err[:, 2]
@@ -558,3 +569,22 @@ def test_expert_physics_completes_kat():
     assert min(phases) >= 6, phases
     assert (epi[:, _lib.EPI["env_error"]] == 0).all()
     print(f"finished within {steps} physics steps; phases visited {phases}")
+
+
+# Each physics-level test on both step layouts: physics_step runs the one-substep kernel of the sim's layout.
+# The test of the 128-row single-wave kernel keeps its name; _l192 is the 192-row kernel with its helper wave.
+
+def test_physics_parity_with_ik_from_oracle_states(margin):
+    _test_physics_parity_with_ik_from_oracle_states(rows=128, margin=margin)
+
+
+def test_physics_parity_with_ik_from_oracle_states_l192(margin):
+    _test_physics_parity_with_ik_from_oracle_states(rows=192, margin=margin)
+
+
+def test_ik_edge_states(margin):
+    _test_ik_edge_states(rows=128, margin=margin)
+
+
+def test_ik_edge_states_l192(margin):
+    _test_ik_edge_states(rows=192, margin=margin)

@@ -274,13 +274,15 @@ def test_oracle_slide_coulomb_bound():
 
 
 # --------------------------------------------------------------------------- GPU (HIP kernel)
-def _gpu_sim(n=1):
+def _gpu_sim(rows, n=1):
     from mujoco_manip_amd import _lib
 
     if not torch.cuda.is_available():
         pytest.skip("needs an MI355X")
     sim = _lib.Sim(n, action_mode="abs_pos", image_size=0)
     sim.reset()  # keyframe (no randomisation)
+    sim.step_rows = rows
+    assert sim.step_rows == rows
     return sim
 
 
@@ -292,10 +294,9 @@ def _gpu_contacts(sim, env=0):
     return con
 
 
-@pytest.mark.gpu
-def test_gpu_rest_penetration():
+def _test_gpu_rest_penetration(rows):
     """The kernel's resting cubes (keyframe, 1 s = 500 substeps) against the closed form."""
-    sim = _gpu_sim()
+    sim = _gpu_sim(rows)
     sim.physics_step(500, with_ik=False)
     q, v, _, _ = sim.get_state()
     con = _gpu_contacts(sim)
@@ -311,9 +312,8 @@ def test_gpu_rest_penetration():
     sim.close()
 
 
-@pytest.mark.gpu
-def test_gpu_free_fall_exact():
-    sim = _gpu_sim()
+def _test_gpu_free_fall_exact(rows):
+    sim = _gpu_sim(rows)
     q, v, c, w = sim.get_state()
     q[0, 9:12], q[0, 12:16] = FALL_X0, FALL_Q0
     v[0, 9:12], v[0, 12:15] = FALL_V0, FALL_W
@@ -328,9 +328,8 @@ def test_gpu_free_fall_exact():
     sim.close()
 
 
-@pytest.mark.gpu
-def test_gpu_slide_first_step_closed_form():
-    sim = _gpu_sim()
+def _test_gpu_slide_first_step_closed_form(rows):
+    sim = _gpu_sim(rows)
     sim.physics_step(500, with_ik=False)
     q, v, c, w = sim.get_state()
     com = _cube(q[0], RED)[0].astype(float)
@@ -349,13 +348,12 @@ def test_gpu_slide_first_step_closed_form():
     sim.close()
 
 
-@pytest.mark.gpu
-def test_gpu_slide_coulomb_bound_and_oracle():
+def _test_gpu_slide_coulomb_bound_and_oracle(rows):
     """The fast push on the device: the Coulomb bound per substep, and the trajectory (a hop and a
     tip: mu = 2 > half-width / half-height) within 1 mm of the oracle's over 40 substeps."""
     import oracle_py as O
 
-    sim = _gpu_sim()
+    sim = _gpu_sim(rows)
     sim.physics_step(500, with_ik=False)
     q, v, c, w = sim.get_state()
     v[0, 9] = 0.5
@@ -375,3 +373,46 @@ def test_gpu_slide_coulomb_bound_and_oracle():
         rq = e.get_state()[0]
         assert np.abs(gq[0, 9:16] - rq[9:16]).max() < 1e-3, (k, gq[0, 9:16], rq[9:16])
     sim.close()
+
+
+# Each physics-level test on both step layouts: physics_step runs the one-substep kernel of the sim's layout.
+# The test of the 128-row single-wave kernel keeps its name; _l192 is the 192-row kernel with its helper wave.
+
+@pytest.mark.gpu
+def test_gpu_rest_penetration():
+    _test_gpu_rest_penetration(rows=128)
+
+
+@pytest.mark.gpu
+def test_gpu_rest_penetration_l192():
+    _test_gpu_rest_penetration(rows=192)
+
+
+@pytest.mark.gpu
+def test_gpu_free_fall_exact():
+    _test_gpu_free_fall_exact(rows=128)
+
+
+@pytest.mark.gpu
+def test_gpu_free_fall_exact_l192():
+    _test_gpu_free_fall_exact(rows=192)
+
+
+@pytest.mark.gpu
+def test_gpu_slide_first_step_closed_form():
+    _test_gpu_slide_first_step_closed_form(rows=128)
+
+
+@pytest.mark.gpu
+def test_gpu_slide_first_step_closed_form_l192():
+    _test_gpu_slide_first_step_closed_form(rows=192)
+
+
+@pytest.mark.gpu
+def test_gpu_slide_coulomb_bound_and_oracle():
+    _test_gpu_slide_coulomb_bound_and_oracle(rows=128)
+
+
+@pytest.mark.gpu
+def test_gpu_slide_coulomb_bound_and_oracle_l192():
+    _test_gpu_slide_coulomb_bound_and_oracle(rows=192)

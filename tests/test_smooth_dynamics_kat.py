@@ -414,9 +414,9 @@ def test_oracle_smooth_terms_and_step(name):
 
 
 # --------------------------------------------------------------------------- HIP kernel (GPU, fp32)
-@pytest.mark.gpu
-def test_gpu_smooth_step_known_answers(margin):
-    """The same scenes through mmx_physics_step (one substep, no IK, ctrl as given) on the kernel."""
+def _test_gpu_smooth_step_known_answers(rows, margin):
+    """The same scenes through mmx_physics_step (one substep, no IK, ctrl as given) on the kernel, on both
+    step layouts (the one-substep kernel of the sim's layout: at 192 rows the helper wave runs the dynamics)."""
     torch = pytest.importorskip("torch")
     if not torch.cuda.is_available():
         pytest.skip("needs an MI355X")
@@ -430,6 +430,8 @@ def test_gpu_smooth_step_known_answers(margin):
     qvel = np.stack([sc[k][1] for k in names]).astype(np.float32)
     ctrl = np.stack([sc[k][2] for k in names]).astype(np.float32)
     sim = _lib.Sim(n, action_mode="abs_pos", image_size=0)
+    sim.step_rows = rows
+    assert sim.step_rows == rows
     sim.set_state(qpos, qvel, ctrl, np.zeros((n, NV), np.float32))
     sim.physics_step(1, with_ik=False)
     gq, gv, _, _ = sim.get_state()
@@ -447,3 +449,16 @@ def test_gpu_smooth_step_known_answers(margin):
         worst = max(worst, dv)
         assert dv < KERNEL_TOL_QVEL, (name, dv, np.abs(gv[k] - want["qvel"]))
         assert dq < 1e-6, (name, dq)
+
+
+# Each physics-level test on both step layouts: physics_step runs the one-substep kernel of the sim's layout.
+# The test of the 128-row single-wave kernel keeps its name; _l192 is the 192-row kernel with its helper wave.
+
+@pytest.mark.gpu
+def test_gpu_smooth_step_known_answers(margin):
+    _test_gpu_smooth_step_known_answers(rows=128, margin=margin)
+
+
+@pytest.mark.gpu
+def test_gpu_smooth_step_known_answers_l192(margin):
+    _test_gpu_smooth_step_known_answers(rows=192, margin=margin)
