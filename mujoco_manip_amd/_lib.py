@@ -8,6 +8,7 @@ fallback.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -330,6 +331,39 @@ class Sim:
                     "mmx_kernel_times")
         return {"step_ms": sm.value, "step_launches": sn.value, "render_ms": rm.value, "render_launches": rn.value}
 
+    @contextlib.contextmanager
+    def _on_sim_stream(self, device):
+        """Run the body on the sim's stream (the encoder and the statistics kernel launch there),
+        ordered after the caller's current stream; on exit the caller's stream waits for the body,
+        whatever stream the caller is on.  Yields (caller's stream, sim's stream)."""
+        import torch
+
+        cur = torch.cuda.current_stream(device)
+        sst = (torch.cuda.ExternalStream(self.cfg.stream, device=device) if self.cfg.stream
+               else torch.cuda.default_stream(device))
+        sst.wait_stream(cur)
+        with torch.cuda.stream(sst):
+            yield cur, sst
+        cur.wait_stream(sst)
+
+    def _png_encode_pack(self, ptr, stride, n, W, H, bound, scr, dev, exact):
+        """mmx_png_encode of n images from `ptr` (`stride` bytes apart), then the files packed back
+        to back (mmx_png_pack) -> (packed, ends int64 [n]), on the current stream.  exact: packed
+        has exactly the files' bytes (a host synchronisation for the size); else room for n * bound."""
+        import torch
+
+        out = torch.empty(n * bound, dtype=torch.uint8, device=dev)
+        scratch = torch.empty(n * scr, dtype=torch.uint8, device=dev)
+        sizes = torch.empty(n, dtype=torch.int32, device=dev)
+        self._check(self.L.mmx_png_encode(self.ptr, C.c_void_p(ptr), stride, n, W, H, C.c_void_p(out.data_ptr()), bound,
+                                          C.c_void_p(sizes.data_ptr()), C.c_void_p(scratch.data_ptr())), "mmx_png_encode")
+        ends = torch.cumsum(sizes.to(torch.int64), 0)
+        starts = ends - sizes.to(torch.int64)
+        packed = torch.empty(int(ends[-1].item()) if exact else n * bound, dtype=torch.uint8, device=dev)
+        self._check(self.L.mmx_png_pack(self.ptr, C.c_void_p(out.data_ptr()), bound, C.c_void_p(sizes.data_ptr()),
+                                        C.c_void_p(starts.data_ptr()), n, C.c_void_p(packed.data_ptr())), "mmx_png_pack")
+        return packed, ends
+
     def png_encode(self, images, max_batch: int = 4096):
         """PNG files of RGB8 images [n, H, W, 3] (a CUDA uint8 tensor, any row-contiguous layout)
         encoded on the device (mmx_png_encode), in batches of `max_batch`.  Returns (packed uint8
@@ -344,44 +378,17 @@ class Sim:
         bound, scr = int(self.L.mmx_png_bound(W, H)), int(self.L.mmx_png_scratch(W, H))
         if bound < 0:
             raise ValueError(f"unsupported image size {W} x {H}")
-        # the encoder runs on the sim's stream: the buffers, the size scan and the read-back are
-        # ordered on that stream too (and the caller's stream waits for the result), whatever
-        # stream the caller is on
-        cur = torch.cuda.current_stream(images.device)
-        sst = (torch.cuda.ExternalStream(self.cfg.stream, device=images.device) if self.cfg.stream
-               else torch.cuda.default_stream(images.device))
-        sst.wait_stream(cur)
-        with torch.cuda.stream(sst):
+        with self._on_sim_stream(images.device) as (cur, sst):  # the buffers, the size scan and the read-back too
             imgs = images.contiguous()
             images.record_stream(sst)
-            packed, offs = self._png_encode_on_stream(imgs, n, H, W, bound, scr, max_batch)
-        cur.wait_stream(sst)
+            parts, offs = [], [0]
+            for b0 in range(0, n, max_batch):
+                m = min(max_batch, n - b0)
+                packed, ends = self._png_encode_pack(imgs[b0].data_ptr(), H * W * 3, m, W, H, bound, scr, imgs.device, True)
+                parts.append(packed)
+                offs.extend((ends.cpu().numpy() + offs[-1]).tolist())
+            packed = torch.cat(parts) if len(parts) > 1 else parts[0]
         packed.record_stream(cur)
-        return packed, offs
-
-    def _png_encode_on_stream(self, imgs, n, H, W, bound, scr, max_batch):
-        import torch
-
-        dev = imgs.device
-        parts, offs = [], [0]
-        for b0 in range(0, n, max_batch):
-            m = min(max_batch, n - b0)
-            out = torch.empty(m * bound, dtype=torch.uint8, device=dev)
-            scratch = torch.empty(m * scr, dtype=torch.uint8, device=dev)
-            sizes = torch.empty(m, dtype=torch.int32, device=dev)
-            self._check(self.L.mmx_png_encode(self.ptr, C.c_void_p(imgs[b0].data_ptr()), H * W * 3, m, W, H,
-                                              C.c_void_p(out.data_ptr()), bound, C.c_void_p(sizes.data_ptr()),
-                                              C.c_void_p(scratch.data_ptr())), "mmx_png_encode")
-            ends = torch.cumsum(sizes.to(torch.int64), 0)
-            starts = ends - sizes.to(torch.int64)
-            total = int(ends[-1].item())
-            packed = torch.empty(total, dtype=torch.uint8, device=dev)
-            self._check(self.L.mmx_png_pack(self.ptr, C.c_void_p(out.data_ptr()), bound, C.c_void_p(sizes.data_ptr()),
-                                            C.c_void_p(starts.data_ptr()), m, C.c_void_p(packed.data_ptr())),
-                        "mmx_png_pack")
-            parts.append(packed)
-            offs.extend((ends.cpu().numpy() + offs[-1]).tolist())
-        packed = torch.cat(parts) if len(parts) > 1 else parts[0]
         return packed, np.asarray(offs, np.int64)
 
     def png_encode_device(self, images):
@@ -398,26 +405,10 @@ class Sim:
         bound, scr = int(self.L.mmx_png_bound(W, H)), int(self.L.mmx_png_scratch(W, H))
         if bound < 0:
             raise ValueError(f"unsupported image size {W} x {H}")
-        cur = torch.cuda.current_stream(images.device)
-        sst = (torch.cuda.ExternalStream(self.cfg.stream, device=images.device) if self.cfg.stream
-               else torch.cuda.default_stream(images.device))
-        sst.wait_stream(cur)
-        dev = images.device
-        with torch.cuda.stream(sst):
+        with self._on_sim_stream(images.device) as (cur, sst):
             images.record_stream(sst)
-            out = torch.empty(n * bound, dtype=torch.uint8, device=dev)
-            scratch = torch.empty(n * scr, dtype=torch.uint8, device=dev)
-            sizes = torch.empty(n, dtype=torch.int32, device=dev)
-            self._check(self.L.mmx_png_encode(self.ptr, C.c_void_p(images.data_ptr()), images.stride(0), n, W, H,
-                                              C.c_void_p(out.data_ptr()), bound, C.c_void_p(sizes.data_ptr()),
-                                              C.c_void_p(scratch.data_ptr())), "mmx_png_encode")
-            ends = torch.cumsum(sizes.to(torch.int64), 0)
-            starts = ends - sizes.to(torch.int64)
-            packed = torch.empty(n * bound, dtype=torch.uint8, device=dev)
-            self._check(self.L.mmx_png_pack(self.ptr, C.c_void_p(out.data_ptr()), bound, C.c_void_p(sizes.data_ptr()),
-                                            C.c_void_p(starts.data_ptr()), n, C.c_void_p(packed.data_ptr())),
-                        "mmx_png_pack")
-        cur.wait_stream(sst)
+            packed, ends = self._png_encode_pack(images.data_ptr(), images.stride(0), n, W, H, bound, scr, images.device,
+                                                 False)
         packed.record_stream(cur)
         ends.record_stream(cur)
         return packed, ends
@@ -434,16 +425,11 @@ class Sim:
         out = torch.empty((n, 4, 3), dtype=torch.int64, device=images.device)
         if n == 0:
             return out
-        cur = torch.cuda.current_stream(images.device)
-        sst = (torch.cuda.ExternalStream(self.cfg.stream, device=images.device) if self.cfg.stream
-               else torch.cuda.default_stream(images.device))
-        sst.wait_stream(cur)
-        with torch.cuda.stream(sst):
+        with self._on_sim_stream(images.device) as (_, sst):
             images.record_stream(sst)
             out.record_stream(sst)
             self._check(self.L.mmx_image_stats(self.ptr, C.c_void_p(images.data_ptr()), images.stride(0), n, W, H,
                                                C.c_void_p(out.data_ptr())), "mmx_image_stats")
-        cur.wait_stream(sst)
         return out
 
     @property

@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from .constants import BINS, OBJECTS, TASK_SETS
-from .dataset import read_lerobot_v3
+from .lerobot import read_lerobot_v3
 
 ACTION_MODES = ("ee_pos_quat_g", "ee_pos_rot6d_g", "ee_pos_quat_g_rel", "ee_pos_rot6d_g_rel")
 

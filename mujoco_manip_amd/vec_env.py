@@ -183,7 +183,7 @@ class PickPlaceVecEnv:
 
     @property
     def step_count(self) -> torch.Tensor:
-        return self._epi[:, 2].clone()
+        return self._epi[:, _lib.EPI["step_count"]].clone()
 
     @property
     def tasks(self) -> list[tuple[str, str]]:
@@ -193,16 +193,16 @@ class PickPlaceVecEnv:
 
     @property
     def fsm_state(self) -> torch.Tensor:
-        return self._epi[:, 4].clone()
+        return self._epi[:, _lib.EPI["fsm_state"]].clone()
 
     @property
     def episode_flags(self) -> torch.Tensor:
         """staged-reward sticky flags: 1 grasped, 2 lifted, 4 above target, 8 placed"""
-        return self._epi[:, 3].clone()
+        return self._epi[:, _lib.EPI["flags"]].clone()
 
     @property
     def env_error(self) -> torch.Tensor:
-        return self._epi[:, 9].clone()
+        return self._epi[:, _lib.EPI["env_error"]].clone()
 
     @property
     def initial_ee_se3(self) -> torch.Tensor:

@@ -292,6 +292,162 @@ def test_copy_ranges_host_helper():
     assert L.mmx_copy_ranges(0, None, None, None) == 0
 
 
+# ---- _EpisodeAssembler (the host side of collect_episodes) on made-up steps: every value is a closed
+# form of (episode, step, column), so the expected episodes are built without the code under test
+class _HostQueue:
+    """Stand-in for the device episode queue (mmx_queue_advance): a free slot takes the next episode
+    in ascending slot order; an episode that has run its length is reported in `fin` at the next
+    advance, when its slot already holds its successor (or -1)."""
+
+    def __init__(self, n_slots, lengths):
+        self.slot, self.left = np.full(n_slots, -1, np.int32), np.zeros(n_slots, np.int64)
+        self.lengths, self.next = lengths, 0
+
+    def advance(self):
+        fin = np.full(len(self.slot), -1, np.int32)
+        for s in range(len(self.slot)):
+            if self.slot[s] >= 0 and self.left[s] == 0:
+                fin[s], self.slot[s] = self.slot[s], -1
+            if self.slot[s] < 0 and self.next < len(self.lengths):
+                self.slot[s], self.left[s] = self.next, self.lengths[self.next]
+                self.next += 1
+        t = np.array([self.lengths[e] - n if e >= 0 else -1 for e, n in zip(self.slot, self.left)])
+        self.left[self.slot >= 0] -= 1
+        return self.slot.copy(), fin, t  # t: the step each slot's episode is at
+
+
+def _asm_row(k, e, t):  # exact in float32: below 2^13, sixteenths
+    return (e * 1000 + t + (np.arange(D.FEATURES[k]["shape"][0]) + NUMERIC.index(k)) / 16).astype(np.float32)
+
+
+def _asm_fsm(e, t):
+    return (e + t) % 11
+
+
+def _asm_file(e, t, cam):  # 9 or 12 bytes in an episode's first step, 21 to 39 later
+    return bytes([e, t % 256, cam]) * (3 + (e + cam) % 2 if t == 0 else 7 + (e + 2 * t + cam) % 7)
+
+
+def _asm_stats(e, t, cam):
+    b, c = e * 10 + t + cam, np.arange(3.0)
+    return np.stack([(b % 5 + c) / 255.0, (200 + b % 13 + c) / 255.0, b + c + 0.5, 2.0 * b + c])
+
+
+_ASM_IMAGE_SIZE = 8
+
+
+def _drive_assembler(lengths, n_slots, feature_keys, sink=None, steps=None):
+    """Feed the assembler the steps of `lengths` episodes in `n_slots` slots until it is over (or
+    for `steps` steps).  Slots without an episode carry junk rows and a junk file, as idle envs do.
+    Returns (assembler, episodes in the order they finished)."""
+    from mujoco_manip_amd import _lib
+
+    tasks = TASK_SETS["all"]
+    eps = [D.Episode(e, *tasks[e % len(tasks)], None) for e in range(len(lengths))]
+    asm = D._EpisodeAssembler(eps, n_slots, feature_keys, _ASM_IMAGE_SIZE,
+                              _lib.load(build_if_missing=False).mmx_copy_ranges, sink)
+    queue, finished, n = _HostQueue(n_slots, lengths), [], 0
+    while (not asm.over) if steps is None else n < steps:
+        slot, fin, t = queue.advance()
+        host = {"_q_slot": slot, "_q_fin": fin,
+                "_fsm": np.array([_asm_fsm(e, i) if e >= 0 else 99 for e, i in zip(slot, t)], np.int32)}
+        for k in NUMERIC:
+            if k in feature_keys:
+                host[k] = np.stack([_asm_row(k, e, i) if e >= 0 else np.full(D.FEATURES[k]["shape"], -7, np.float32)
+                                    for e, i in zip(slot, t)])
+        png = {}
+        for cam, k in enumerate(D.IMAGE_KEYS):
+            if k in feature_keys:
+                files = [_asm_file(e, i, cam) if e >= 0 else b"\xee" * 5 for e, i in zip(slot, t)]
+                png[k] = np.frombuffer(b"".join(files), np.uint8)
+                host[k + "/ends"] = np.cumsum([len(f) for f in files]).astype(np.int64)
+                host[k + "/stats"] = np.stack([_asm_stats(e, i, cam) if e >= 0 else np.full((4, 3), np.nan)
+                                               for e, i in zip(slot, t)])
+        asm.step(host, png)
+        left = set(range(asm.emitted)) | set(asm.done_eps)
+        finished += sorted(left - set(finished))
+        n += 1
+        assert n < 1000
+    return asm, finished
+
+
+def _check_assembled(ep, e, length, feature_keys):
+    """Episode `ep` against episode e's closed forms, exactly."""
+    obj, bin_ = TASK_SETS["all"][e % len(TASK_SETS["all"])]
+    assert (ep.obj, ep.bin, ep.seed, ep.length) == (obj, bin_, None, length)
+    for k in feature_keys:
+        if k in D.IMAGE_KEYS:
+            cam = D.IMAGE_KEYS.index(k)
+            files = [_asm_file(e, t, cam) for t in range(length)]
+            fr = ep.frames[k]
+            assert isinstance(fr, D.PngFrames) and len(fr) == length
+            assert [fr[t] for t in range(length)] == files
+            assert fr.offsets.tolist() == np.cumsum([0] + [len(f) for f in files]).tolist()
+            assert fr.nbytes == sum(map(len, files)) == len(fr.data)
+            want = D._merge_image_stats(np.stack([_asm_stats(e, t, cam) for t in range(length)]),
+                                        _ASM_IMAGE_SIZE * _ASM_IMAGE_SIZE)
+            assert ep.image_stats[k] == want
+        elif k == "observation.phase_description":
+            assert ep.frames[k] == [D.phase_description(_asm_fsm(e, t), obj, bin_) for t in range(length)]
+        else:
+            want = np.stack([_asm_row(k, e, t) for t in range(length)])
+            assert ep.frames[k].dtype == np.float32 and ep.frames[k].shape == want.shape
+            assert (ep.frames[k] == want).all()
+    assert set(ep.frames) == set(feature_keys)
+
+
+_ASM_LENGTHS = [1, 70, 2, 65, 3, 1, 130, 2]
+
+
+@pytest.mark.parametrize("kinds", ["all", "numeric"])
+def test_episode_assembler_rebuilds_episodes(kinds):
+    """3 slots, 8 episodes of 1 to 130 steps: rows past the 64- and the 128-row capacity, PNG buffers
+    past the first-step guess (bytes carried over), slots reused in the step their episode is reported
+    finished, episodes finishing out of index order, one-step episodes.  With a sink (in index order,
+    nothing kept) and as a list."""
+    import gc
+    import weakref
+
+    keys = set(D.FEATURES) if kinds == "all" else set(NUMERIC)
+    got, refs = [], []
+
+    def sink(ep):
+        got.append(ep.index)
+        refs.append(weakref.ref(ep))
+        _check_assembled(ep, ep.index, _ASM_LENGTHS[ep.index], keys)
+
+    asm, finished = _drive_assembler(_ASM_LENGTHS, 3, keys, sink)
+    assert got == list(range(8)) and asm.episodes is None and asm.open_ids() == []
+    assert asm.eps == [None] * 8 and not asm.done_eps
+    gc.collect()
+    assert all(r() is None for r in refs)  # the assembler kept no reference to what the sink took
+    assert all(b is None for bufs in asm.png_buf.values() for b in bufs)  # the PNG buffers went with the episodes
+    # the cases happened: both capacity doublings, a PNG buffer regrown with bytes kept, out-of-order ends
+    assert asm.cap > 128
+    assert sorted(finished) == list(range(8)) and finished != sorted(finished)
+    if kinds == "all":
+        assert asm.png_regrown > 0
+
+    asm, _ = _drive_assembler(_ASM_LENGTHS, 3, keys)
+    assert [ep.index for ep in asm.episodes] == list(range(8)) and asm.episodes == asm.eps
+    for ep in asm.episodes:
+        _check_assembled(ep, ep.index, _ASM_LENGTHS[ep.index], keys)
+
+
+def test_episode_assembler_closes_open_episodes():
+    """close_open after three steps of one slot: the running episode comes out with the rows it has,
+    the one that never ran with length 0, empty frames and no image statistics; the sink gets both."""
+    keys = set(D.FEATURES)
+    got = []
+    asm, _ = _drive_assembler([5, 3], 1, keys, got.append, steps=3)
+    assert got == [] and asm.open_ids() == [0, 1] and not asm.over
+    asm.close_open()
+    assert [ep.index for ep in got] == [0, 1] and asm.open_ids() == [] and asm.eps == [None, None]
+    _check_assembled(got[0], 0, 3, keys)
+    assert got[1].length == 0 and all(len(v) == 0 for v in got[1].frames.values())
+    assert got[1].image_stats == {k: None for k in D.IMAGE_KEYS}
+
+
 def test_threaded_writer_reports_errors(tmp_path):
     rng = np.random.default_rng(4)
     feats = {"observation.state": D.FEATURES["observation.state"]}
