@@ -176,6 +176,53 @@ int mmx_rollout_actions(mmx_sim* sim, const float* actions_dev, int32_t action_d
                         const mmx_trajectory* rec);
 int mmx_rollout_expert_record(mmx_sim* sim, int32_t n_env_steps, const mmx_trajectory* rec);
 
+/* Snapshot and restore of whole environments on the device, one to many (no reference counterpart: the
+ * reference has one env per process and no state setter; sampling planners, branching data collection,
+ * curriculum restarts and failure debugging start many envs from one state).  A restored env continues
+ * bit for bit as the env the record was taken from would have: a record holds every per-env array a
+ * launch reads or a facade returns, in this fixed order (_lib.SNAPSHOT_FIELDS mirrors it):
+ *     rng                [4] uint64   PCG64 state hi, lo, increment hi, lo
+ *     rng32              [1] uint32   buffered upper half of the last 64-bit draw
+ *     qpos               [30] fp32
+ *     qvel               [27] fp32
+ *     ctrl               [8] fp32
+ *     qacc_warmstart     [27] fp32
+ *     kin                [63] fp32    the stale kinematics cache the IK and the FSM read
+ *     target             [4] fp32
+ *     episode_i          [18] int32   whole, the sticky counters included: a branch is a copy
+ *     episode_f          [28] fp32
+ *     obs                [85] fp32
+ *     reward             [1] fp32
+ *     reward_components  [6] fp32
+ *     done               [3] int32
+ *     rpose              [168] fp32   body poses the cameras draw from; only when image_size > 0
+ * The fields are packed (1236 bytes) and padded to MMX_SNAPSHOT_BYTES = 1248; a sim with cameras appends
+ * rpose there: MMX_SNAPSHOT_BYTES_CAMERAS = 1920.  mmx_snapshot_bytes returns the sim's record size (-1 for
+ * a NULL sim); it depends on nothing else in the configuration.
+ * Not in a record: contacts and stats (diagnostics of the last launch; the next step overwrites them), the
+ * images and segment ids (redrawn on restore), the episode queue's slot table, the sim-level
+ * sampling-fault flag (MMX_ESAMPLING) and the configuration.
+ * mmx_snapshot writes N records into caller-owned device memory, 16-byte aligned: record i is env i, at
+ * snap_dev + i * rec_bytes.  mmx_restore: env i takes record src_dev[i] (device int32 [N]) of the n_records
+ * records at snap_dev; -1, or any value outside [0, n_records), leaves env i exactly as it is and nothing
+ * outside the blob is ever read; src_dev == NULL: env i takes record i where i < n_records and is kept
+ * otherwise.  One record may go to any number of envs (the branch).  With cameras the restored envs, and
+ * only those, are re-rendered from the restored poses with the sim's current render effects: their images
+ * and seg are then what they were at snapshot time (under the same effects).
+ * Both are asynchronous on the sim's stream, ordered with steps and rollouts like any other launch.
+ * MMX_EINVAL, with nothing launched, for a NULL sim, a NULL (or not 16-byte aligned) blob, rec_bytes !=
+ * mmx_snapshot_bytes(sim), or n_records < 0; n_records == 0 does nothing and returns MMX_OK.
+ * A blob may be restored into another sim of the same process and device, with another num_envs and
+ * another step layout; the record size rejects a camera / no-camera mismatch.  A different action mode,
+ * reward type, episode limit or solver setting between the two sims is the caller's responsibility: the
+ * record carries state, not configuration. */
+#define MMX_SNAPSHOT_BYTES 1248
+#define MMX_SNAPSHOT_BYTES_CAMERAS 1920
+int64_t mmx_snapshot_bytes(const mmx_sim* sim);
+int mmx_snapshot(mmx_sim* sim, void* snap_dev, int64_t rec_bytes);
+int mmx_restore(mmx_sim* sim, const void* snap_dev, int64_t rec_bytes, int32_t n_records,
+                const int32_t* src_dev);
+
 /* Batched PNG encoder (dataset emission, generate_dataset.py:250-260: LeRobot embeds image
  * features as PNG files).  Encodes n RGB8 images (device, image i at rgb_dev + i * img_stride,
  * rows of 3 * width bytes, height <= 1024, width <= MMX_PNG_MAX_WIDTH: the encoder's row-above match

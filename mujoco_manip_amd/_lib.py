@@ -84,6 +84,35 @@ TRAJ_FIELDS = {"obs": (NOBS, "float32"), "reward": (1, "float32"), "done": (3, "
                "reward_components": (6, "float32"), "target": (4, "float32"), "episode_i": (EPI_N, "int32"),
                "qpos": (NQ, "float32"), "qvel": (NV, "float32")}
 
+# One env's snapshot record (include/mmx_api.h, mmx_snapshot / mmx_restore): (name, width, dtype) in the
+# record's order; the fields are packed and the record padded to 16 bytes, rpose (cameras only) follows
+RPOSE_N = 14 * 12  # body poses the cameras draw from: 14 slots x (R row-major 9, p 3)
+SNAPSHOT_FIELDS = (("rng", 4, "uint64"), ("rng32", 1, "uint32"), ("qpos", NQ, "float32"), ("qvel", NV, "float32"),
+                   ("ctrl", NU, "float32"), ("qacc_warmstart", NV, "float32"), ("kin", KIN_N, "float32"),
+                   ("target", 4, "float32"), ("episode_i", EPI_N, "int32"), ("episode_f", EPF_N, "float32"),
+                   ("obs", NOBS, "float32"), ("reward", 1, "float32"), ("reward_components", 6, "float32"),
+                   ("done", 3, "int32"), ("rpose", RPOSE_N, "float32"))
+
+
+def snapshot_record_bytes(cameras: bool) -> int:
+    """Bytes of one record: the packed fields without rpose, padded to 16, then rpose with cameras."""
+    fixed = sum(w * np.dtype(t).itemsize for name, w, t in SNAPSHOT_FIELDS if name != "rpose")
+    return -(-fixed // 16) * 16 + (RPOSE_N * 4 if cameras else 0)
+
+
+def snapshot_field_offsets(cameras: bool) -> dict:
+    """{name: (byte offset, width, dtype)} of the fields of a record (a uint8 row of a Snapshot's tensor)."""
+    out, off = {}, 0
+    for name, w, t in SNAPSHOT_FIELDS:
+        if name == "rpose":
+            if not cameras:
+                continue
+            off = -(-off // 16) * 16
+        out[name] = (off, w, t)
+        off += w * np.dtype(t).itemsize
+    return out
+
+
 EXPORTED = ("mmx_config_default", "mmx_create", "mmx_destroy", "mmx_last_error", "mmx_reset", "mmx_step",
             "mmx_expert_plan", "mmx_rollout_expert", "mmx_physics_step", "mmx_forward", "mmx_get_buffers",
             "mmx_synchronize", "mmx_get_state", "mmx_set_state", "mmx_episode_seed", "mmx_rollout_lanes",
@@ -91,7 +120,8 @@ EXPORTED = ("mmx_config_default", "mmx_create", "mmx_destroy", "mmx_last_error",
             "mmx_kernel_times", "mmx_png_bound", "mmx_png_scratch", "mmx_png_encode", "mmx_png_pack", "mmx_image_stats",
             "mmx_queue_init", "mmx_queue_advance", "mmx_set_step_rows", "mmx_step_rows", "mmx_copy_ranges", "mmx_rollout_render_launches",
             "mmx_set_step_order", "mmx_step_order", "mmx_rollout_render_overlap", "mmx_set_render_effects",
-            "mmx_get_render_effects", "mmx_rollout_actions", "mmx_rollout_expert_record")
+            "mmx_get_render_effects", "mmx_rollout_actions", "mmx_rollout_expert_record", "mmx_snapshot_bytes",
+            "mmx_snapshot", "mmx_restore")
 
 _lib = None
 
@@ -121,6 +151,10 @@ def load(build_if_missing: bool = True):
     L.mmx_rollout_expert.argtypes = [vp, C.c_int32]
     L.mmx_rollout_actions.argtypes = [vp, vp, C.c_int32, C.c_int32, C.POINTER(MMXTrajectory)]
     L.mmx_rollout_expert_record.argtypes = [vp, C.c_int32, C.POINTER(MMXTrajectory)]
+    L.mmx_snapshot_bytes.argtypes = [vp]
+    L.mmx_snapshot_bytes.restype = C.c_int64
+    L.mmx_snapshot.argtypes = [vp, vp, C.c_int64]
+    L.mmx_restore.argtypes = [vp, vp, C.c_int64, C.c_int32, vp]
     L.mmx_physics_step.argtypes = [vp, C.c_int32, C.c_int32]
     L.mmx_rollout_lanes.argtypes = [vp]
     L.mmx_rollout_lanes.restype = C.c_int
@@ -167,7 +201,7 @@ def load(build_if_missing: bool = True):
                  "mmx_forward", "mmx_get_buffers", "mmx_synchronize", "mmx_get_state", "mmx_set_state",
                  "mmx_expert_physics", "mmx_eval_reward", "mmx_kernel_timing", "mmx_kernel_times", "mmx_png_encode",
                  "mmx_png_pack", "mmx_image_stats", "mmx_queue_init", "mmx_queue_advance", "mmx_set_step_rows", "mmx_set_step_order",
-                 "mmx_set_render_effects", "mmx_rollout_actions", "mmx_rollout_expert_record"):
+                 "mmx_set_render_effects", "mmx_rollout_actions", "mmx_rollout_expert_record", "mmx_snapshot", "mmx_restore"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -319,6 +353,23 @@ class Sim:
         """n_env_steps through the device actions [T][N][action_dim] in fused launches (mmx_rollout_actions)."""
         self._check(self.L.mmx_rollout_actions(self.ptr, C.c_void_p(actions_ptr), action_dim, n_env_steps,
                                                None if record is None else C.byref(record)), "mmx_rollout_actions")
+
+    @property
+    def snapshot_bytes(self) -> int:
+        """Bytes of one env's snapshot record for this sim (mmx_snapshot_bytes: larger with cameras)."""
+        return int(self.L.mmx_snapshot_bytes(self.ptr))
+
+    def snapshot(self, ptr: int):
+        """Write every env's record to device memory at `ptr` (num_envs * snapshot_bytes bytes, 16-byte
+        aligned): record i = env i (mmx_snapshot; asynchronous on the sim's stream)."""
+        self._check(self.L.mmx_snapshot(self.ptr, C.c_void_p(ptr), self.snapshot_bytes), "mmx_snapshot")
+
+    def restore(self, ptr: int, n_records: int, src_ptr: int | None = None):
+        """Env i takes record src[i] of the n_records records at `ptr` (src_ptr: device int32 [num_envs];
+        an index outside [0, n_records) keeps the env; None: env i takes record i where there is one);
+        with cameras the restored envs are re-rendered (mmx_restore; asynchronous on the sim's stream)."""
+        self._check(self.L.mmx_restore(self.ptr, C.c_void_p(ptr), self.snapshot_bytes, int(n_records),
+                                       C.c_void_p(src_ptr) if src_ptr else None), "mmx_restore")
 
     def kernel_timing(self, enable: bool):
         """Start (True: a new collection) / stop bracketing every rollout launch with HIP events."""

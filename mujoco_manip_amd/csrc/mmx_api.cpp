@@ -48,6 +48,10 @@ extern "C" hipError_t mmx_launch_image_stats(const uint8_t* rgb, int64_t img_str
                                              hipStream_t st);
 extern "C" int64_t mmx_png_bound_bytes(int width, int height);
 extern "C" int64_t mmx_png_scratch_bytes(int width, int height);
+extern "C" int64_t mmx_snapshot_record_bytes(int cameras);
+extern "C" hipError_t mmx_launch_snapshot(const MMXState* S, void* blob, hipStream_t st);
+extern "C" hipError_t mmx_launch_restore(const MMXState* S, const void* blob, int n_records, const int* src,
+                                         unsigned char* mask, hipStream_t st);
 extern "C" hipError_t mmx_launch_expert_physics(const MMXState* S, int n, hipStream_t st);
 extern "C" hipError_t mmx_launch_reward(const MMXState* S, const float* obj, const float* ee, const float* ctrl7,
                                         const int* pairs, int max_pairs, hipStream_t st);
@@ -915,6 +919,34 @@ int mmx_set_state(mmx_sim* sim, const float* qpos, const float* qvel, const floa
   if (e == hipSuccess && ctrl) e = hipMemcpy(sim->S.ctrl, ctrl, MMX_NU_ * n * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess && ws) e = hipMemcpy(sim->S.qacc_ws, ws, MMX_NV_ * n * 4, hipMemcpyHostToDevice);
   return hip_check(sim, e, "mmx_set_state");
+}
+
+// Snapshot / restore (mmx_snapshot.hip).  A record's size depends on the cameras only (the body poses).
+int64_t mmx_snapshot_bytes(const mmx_sim* sim) { return sim ? mmx_snapshot_record_bytes(sim->S.image_size > 0) : -1; }
+
+static bool snapshot_args_ok(const mmx_sim* sim, const void* blob, int64_t rec_bytes) {
+  return sim && blob && reinterpret_cast<uintptr_t>(blob) % 16 == 0 && rec_bytes == mmx_snapshot_bytes(sim);
+}
+
+int mmx_snapshot(mmx_sim* sim, void* snap_dev, int64_t rec_bytes) {
+  if (!snapshot_args_ok(sim, snap_dev, rec_bytes))
+    return sim ? fail(sim, MMX_EINVAL, "mmx_snapshot: bad arguments (NULL or unaligned blob, or not this sim's record size)") : MMX_EINVAL;
+  DeviceGuard guard(sim);
+  return hip_check(sim, mmx_launch_snapshot(&sim->S, snap_dev, sim->stream), "mmx_snapshot");
+}
+
+int mmx_restore(mmx_sim* sim, const void* snap_dev, int64_t rec_bytes, int32_t n_records, const int32_t* src_dev) {
+  if (!snapshot_args_ok(sim, snap_dev, rec_bytes) || n_records < 0)
+    return sim ? fail(sim, MMX_EINVAL, "mmx_restore: bad arguments (NULL or unaligned blob, not this sim's record size, or n_records < 0)")
+               : MMX_EINVAL;
+  if (n_records == 0) return MMX_OK;
+  DeviceGuard guard(sim);
+  const MMXState& S = sim->S;  // S.rpose: the pose buffer that is current now (camera rollouts swap it)
+  unsigned char* mask = S.image_size > 0 ? sim->d_mask : nullptr;
+  hipError_t e = mmx_launch_restore(&S, snap_dev, n_records, src_dev, mask, sim->stream);
+  // the restored envs' images and segment ids, redrawn from the restored poses with the sim's current effects
+  if (e == hipSuccess && mask) e = mmx_launch_render_masked(&S, 0, S.N, mask, sim->stream);
+  return hip_check(sim, e, "mmx_restore");
 }
 
 int mmx_queue_init(mmx_sim* sim, int32_t n_episodes, const uint64_t* seeds, const int32_t* tasks) {

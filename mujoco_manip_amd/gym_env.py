@@ -234,6 +234,16 @@ class PickPlaceGymEnv(_Base):
         return ({k: v[0].cpu().numpy() for k, v in obs.items()}, float(r[0].item()), bool(term[0].item()),
                 bool(trunc[0].item()), out_info)
 
+    def snapshot(self):
+        """The env's whole state on the device (PickPlaceVecEnv.snapshot): a Snapshot of one record."""
+        return self._vec.snapshot()
+
+    def restore(self, snap, src: int | None = None):
+        """Put the env back to a snapshot's state (record `src` of it, the first by default); returns
+        (obs, info) like reset.  The snapshot may come from a PickPlaceVecEnv with the same record size."""
+        obs, info = self._vec.restore(snap, src=0 if src is None else int(src))
+        return {k: v[0].cpu().numpy() for k, v in obs.items()}, info
+
     def expert_action(self, n_steps: int = ACTION_REPEAT) -> np.ndarray:
         """PickAndPlaceTask.plan(n_steps) + abs_pos action (generate_dataset.py:142-148)."""
         return self._vec.expert_plan(n_steps)[0].cpu().numpy()

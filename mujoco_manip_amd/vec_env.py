@@ -30,6 +30,21 @@ def split_obs(flat: torch.Tensor) -> dict:
     return {k: flat[..., a:b].reshape(*flat.shape[:-1], *shape) for k, (a, b, shape) in OBS_SLICES.items()}
 
 
+class Snapshot:
+    """The state of `num_envs` environments on the device (PickPlaceVecEnv.snapshot): `data` is the uint8
+    tensor [num_envs, rec_bytes] of their records (include/mmx_api.h; _lib.snapshot_field_offsets gives
+    the fields of a row).  It may be restored any number of times, into any env with the same record size
+    (cameras or not) on the same device, whatever its num_envs."""
+
+    def __init__(self, data: torch.Tensor):
+        assert data.dtype == torch.uint8 and data.dim() == 2 and data.is_contiguous()
+        self.data = data
+        self.num_envs, self.rec_bytes = int(data.shape[0]), int(data.shape[1])
+
+    def clone(self) -> "Snapshot":
+        return Snapshot(self.data.clone())
+
+
 class PickPlaceVecEnv:
     metadata = {"render_modes": [], "render_fps": 30}
 
@@ -180,6 +195,46 @@ class PickPlaceVecEnv:
             self.sim.rollout_actions(a.data_ptr(), a.shape[2], T, rec)
             self._last_action = a
         return out
+
+    # ------------------------------------------------------------------ snapshot / restore
+    def snapshot(self) -> Snapshot:
+        """The state of every env, on the device (mmx_snapshot; asynchronous): everything a step reads and
+        a reset / step returns, so a restored env continues bit for bit as this one does from here.  Not
+        held: contacts and solver statistics of the last launch, the images (redrawn on restore), the
+        dataset episode queue, the configuration."""
+        data = torch.empty((self.num_envs, self.sim.snapshot_bytes), dtype=torch.uint8, device=self.device)
+        self.sim.snapshot(data.data_ptr())
+        return Snapshot(data)
+
+    def restore(self, snap: Snapshot, src=None):
+        """Put envs back to states of `snap`; returns (obs, info) like reset.  src None: env i takes record i
+        (envs past the snapshot's last record are kept); an int: every env takes that record (the branch of
+        a sampling planner); an int sequence or tensor [num_envs]: env i takes record src[i], -1 (or any
+        index outside the snapshot) keeps env i as it is.  With cameras the restored envs are re-rendered.
+        The snapshot may come from another env with the same record size (cameras or not); a different
+        action mode, reward type or episode limit there is the caller's responsibility."""
+        if not isinstance(snap, Snapshot):
+            raise TypeError("restore needs a Snapshot (PickPlaceVecEnv.snapshot())")
+        if snap.rec_bytes != self.sim.snapshot_bytes:
+            raise ValueError(f"snapshot records have {snap.rec_bytes} bytes, this env's {self.sim.snapshot_bytes} "
+                             "(a snapshot with cameras cannot go to an env without, or back)")
+        if snap.data.device != self.device:
+            raise ValueError(f"snapshot is on {snap.data.device}, this env on {self.device}")
+        idx = None
+        if src is not None:
+            if isinstance(src, (int, np.integer)):
+                idx = torch.full((self.num_envs,), int(src), dtype=torch.int32, device=self.device)
+            else:
+                idx = torch.as_tensor(src, device=self.device)
+                if idx.dim() != 1 or idx.shape[0] != self.num_envs or idx.dtype.is_floating_point:
+                    raise ValueError(f"src must be None, an int or {self.num_envs} ints, got shape {tuple(idx.shape)} "
+                                     f"of {idx.dtype}")
+                if idx.dtype != torch.int32:  # (an int64 index past 2^31 must not wrap into the snapshot)
+                    idx = torch.where((idx >= 0) & (idx < snap.num_envs), idx, -1).to(torch.int32)
+                idx = idx.contiguous()
+        self.sim.restore(snap.data.data_ptr(), snap.num_envs, None if idx is None else idx.data_ptr())
+        self._last_src = idx
+        return self._obs_dict(), {}
 
     @property
     def step_count(self) -> torch.Tensor:

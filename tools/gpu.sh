@@ -23,6 +23,9 @@
 #                    without its per-step record, the expert rollout with and without; BASELINE_LIB = a
 #                    library of the baseline commit adds its step loop (line a); TRAJ_OUT = a file for the
 #                    full result (the summary line goes to stdout either way)
+#   snapshot         snapshot / restore timing beside one step launch and the host state round trip
+#                    (tools/snapshot_time.py); SNAP_OUT = a file for the full result (default
+#                    profiles/r10_snapshot.json)
 # Env: R (round tag, default r06), MMX_LIB_PATH (a library other than the product for every recipe).
 set -o pipefail
 cd ${GRAFT_REPO_ROOT:-$(pwd)}; ROOT=$(pwd); mkdir -p gpurun_out
@@ -152,6 +155,7 @@ for recipe in "$@"; do
     ab) bash tools/ab.sh ;;
     occupancy) occupancy ;;
     traj) traj ;;
+    snapshot) timeout -k 10 300 python -u tools/snapshot_time.py ${SNAP_OUT:+--out $SNAP_OUT} ;;
     *) echo "unknown recipe $recipe"; false ;;
   esac || exit $?
 done
