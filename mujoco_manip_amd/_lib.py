@@ -113,15 +113,57 @@ def snapshot_field_offsets(cameras: bool) -> dict:
     return out
 
 
-EXPORTED = ("mmx_config_default", "mmx_create", "mmx_destroy", "mmx_last_error", "mmx_reset", "mmx_step",
-            "mmx_expert_plan", "mmx_rollout_expert", "mmx_physics_step", "mmx_forward", "mmx_get_buffers",
-            "mmx_synchronize", "mmx_get_state", "mmx_set_state", "mmx_episode_seed", "mmx_rollout_lanes",
-            "mmx_rollout_steps_per_launch", "mmx_rollout_launches", "mmx_expert_physics", "mmx_eval_reward", "mmx_kernel_timing",
-            "mmx_kernel_times", "mmx_png_bound", "mmx_png_scratch", "mmx_png_encode", "mmx_png_pack", "mmx_image_stats",
-            "mmx_queue_init", "mmx_queue_advance", "mmx_set_step_rows", "mmx_step_rows", "mmx_copy_ranges", "mmx_rollout_render_launches",
-            "mmx_set_step_order", "mmx_step_order", "mmx_rollout_render_overlap", "mmx_set_render_effects",
-            "mmx_get_render_effects", "mmx_rollout_actions", "mmx_rollout_expert_record", "mmx_snapshot_bytes",
-            "mmx_snapshot", "mmx_restore")
+_vp, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
+_u8p, _i32p, _u64p, _fp = C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_float)
+# Every C-ABI function, name -> (restype, argtypes), in the headers' order; load() applies it
+_PROTOS = {
+    # include/mmx_api.h
+    "mmx_config_default": (None, [C.POINTER(MMXConfig)]),
+    "mmx_create": (C.c_int, [C.POINTER(MMXConfig), C.POINTER(_vp)]),
+    "mmx_destroy": (None, [_vp]),
+    "mmx_last_error": (C.c_char_p, [_vp]),
+    "mmx_reset": (C.c_int, [_vp, _u64p, _u8p, _i32p, _u8p]),
+    "mmx_step": (C.c_int, [_vp, _vp, _i32]),
+    "mmx_copy_ranges": (_i64, [_i64, _vp, _vp, _vp]),
+    "mmx_expert_plan": (C.c_int, [_vp, _i32, _vp]),
+    "mmx_rollout_expert": (C.c_int, [_vp, _i32]),
+    "mmx_rollout_actions": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(MMXTrajectory)]),
+    "mmx_rollout_expert_record": (C.c_int, [_vp, _i32, C.POINTER(MMXTrajectory)]),
+    "mmx_snapshot_bytes": (_i64, [_vp]),
+    "mmx_snapshot": (C.c_int, [_vp, _vp, _i64]),
+    "mmx_restore": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
+    "mmx_png_bound": (_i64, [_i32, _i32]),
+    "mmx_png_scratch": (_i64, [_i32, _i32]),
+    "mmx_png_encode": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "mmx_png_pack": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i32, _vp]),
+    "mmx_image_stats": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    "mmx_physics_step": (C.c_int, [_vp, _i32, _i32]),
+    "mmx_forward": (C.c_int, [_vp]),
+    "mmx_expert_physics": (C.c_int, [_vp, _i32]),
+    "mmx_eval_reward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32]),
+    "mmx_set_render_effects": (C.c_int, [_vp, _i32]),
+    "mmx_get_render_effects": (C.c_int, [_vp]),
+    "mmx_get_buffers": (C.c_int, [_vp, C.POINTER(MMXBuffers)]),
+    "mmx_synchronize": (C.c_int, [_vp]),
+    "mmx_get_state": (C.c_int, [_vp, _fp, _fp, _fp, _fp]),
+    "mmx_set_state": (C.c_int, [_vp, _fp, _fp, _fp, _fp]),
+    "mmx_queue_init": (C.c_int, [_vp, _i32, _u64p, _i32p]),
+    "mmx_queue_advance": (C.c_int, [_vp, _vp, _vp]),
+    "mmx_episode_seed": (C.c_uint32, [C.c_uint64, _i32]),
+    # include/mmx_tuning.h
+    "mmx_set_step_rows": (C.c_int, [_vp, _i32]),
+    "mmx_step_rows": (C.c_int, [_vp]),
+    "mmx_set_step_order": (C.c_int, [_vp, _i32]),
+    "mmx_step_order": (C.c_int, [_vp]),
+    "mmx_rollout_launches": (C.c_int, [_vp, _i32]),
+    "mmx_rollout_lanes": (C.c_int, [_vp]),
+    "mmx_rollout_render_launches": (C.c_int, [_vp]),
+    "mmx_rollout_render_overlap": (C.c_int, [_vp]),
+    "mmx_rollout_steps_per_launch": (C.c_int, [_vp]),
+    "mmx_kernel_timing": (C.c_int, [_vp, _i32]),
+    "mmx_kernel_times": (C.c_int, [_vp, _fp, _i32p, _fp, _i32p]),
+}
+EXPORTED = tuple(_PROTOS)
 
 _lib = None
 
@@ -139,70 +181,9 @@ def load(build_if_missing: bool = True):
             raise RuntimeError(f"{os.path.basename(path)} missing at {path}; run __graft_entry__.build()")
         _build.build(profile=profile)
     L = C.CDLL(path)
-    vp, u8p, i32p, u64p, fp = C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_float)
-    L.mmx_config_default.argtypes = [C.POINTER(MMXConfig)]
-    L.mmx_create.argtypes = [C.POINTER(MMXConfig), C.POINTER(vp)]
-    L.mmx_destroy.argtypes = [vp]
-    L.mmx_last_error.restype = C.c_char_p
-    L.mmx_last_error.argtypes = [vp]
-    L.mmx_reset.argtypes = [vp, u64p, u8p, i32p, u8p]
-    L.mmx_step.argtypes = [vp, vp, C.c_int32]
-    L.mmx_expert_plan.argtypes = [vp, C.c_int32, vp]
-    L.mmx_rollout_expert.argtypes = [vp, C.c_int32]
-    L.mmx_rollout_actions.argtypes = [vp, vp, C.c_int32, C.c_int32, C.POINTER(MMXTrajectory)]
-    L.mmx_rollout_expert_record.argtypes = [vp, C.c_int32, C.POINTER(MMXTrajectory)]
-    L.mmx_snapshot_bytes.argtypes = [vp]
-    L.mmx_snapshot_bytes.restype = C.c_int64
-    L.mmx_snapshot.argtypes = [vp, vp, C.c_int64]
-    L.mmx_restore.argtypes = [vp, vp, C.c_int64, C.c_int32, vp]
-    L.mmx_physics_step.argtypes = [vp, C.c_int32, C.c_int32]
-    L.mmx_rollout_lanes.argtypes = [vp]
-    L.mmx_rollout_lanes.restype = C.c_int
-    L.mmx_rollout_render_launches.argtypes = [vp]
-    L.mmx_rollout_render_launches.restype = C.c_int
-    L.mmx_copy_ranges.argtypes = [C.c_int64, vp, vp, vp]
-    L.mmx_copy_ranges.restype = C.c_int64
-    L.mmx_set_step_rows.argtypes = [vp, C.c_int32]
-    L.mmx_step_rows.argtypes = [vp]
-    L.mmx_step_rows.restype = C.c_int
-    L.mmx_set_step_order.argtypes = [vp, C.c_int32]
-    L.mmx_rollout_render_overlap.argtypes = [vp]
-    L.mmx_rollout_render_overlap.restype = C.c_int
-    L.mmx_step_order.argtypes = [vp]
-    L.mmx_set_render_effects.argtypes = [vp, C.c_int32]
-    L.mmx_get_render_effects.argtypes = [vp]
-    L.mmx_get_render_effects.restype = C.c_int
-    L.mmx_step_order.restype = C.c_int
-    L.mmx_rollout_steps_per_launch.argtypes = [vp]
-    L.mmx_rollout_steps_per_launch.restype = C.c_int
-    L.mmx_rollout_launches.argtypes = [vp, C.c_int32]
-    L.mmx_rollout_launches.restype = C.c_int
-    L.mmx_forward.argtypes = [vp]
-    L.mmx_expert_physics.argtypes = [vp, C.c_int32]
-    L.mmx_eval_reward.argtypes = [vp, vp, vp, vp, vp, C.c_int32]
-    L.mmx_kernel_timing.argtypes = [vp, C.c_int32]
-    L.mmx_png_bound.argtypes = [C.c_int32, C.c_int32]
-    L.mmx_png_bound.restype = C.c_int64
-    L.mmx_png_scratch.argtypes = [C.c_int32, C.c_int32]
-    L.mmx_png_scratch.restype = C.c_int64
-    L.mmx_png_encode.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64, vp, vp]
-    L.mmx_png_pack.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int32, vp]
-    L.mmx_image_stats.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp]
-    L.mmx_kernel_times.argtypes = [vp, fp, i32p, fp, i32p]
-    L.mmx_get_buffers.argtypes = [vp, C.POINTER(MMXBuffers)]
-    L.mmx_synchronize.argtypes = [vp]
-    L.mmx_get_state.argtypes = [vp, fp, fp, fp, fp]
-    L.mmx_set_state.argtypes = [vp, fp, fp, fp, fp]
-    L.mmx_queue_init.argtypes = [vp, C.c_int32, u64p, i32p]
-    L.mmx_queue_advance.argtypes = [vp, vp, vp]
-    L.mmx_episode_seed.restype = C.c_uint32
-    L.mmx_episode_seed.argtypes = [C.c_uint64, C.c_int32]
-    for name in ("mmx_create", "mmx_reset", "mmx_step", "mmx_expert_plan", "mmx_rollout_expert", "mmx_physics_step",
-                 "mmx_forward", "mmx_get_buffers", "mmx_synchronize", "mmx_get_state", "mmx_set_state",
-                 "mmx_expert_physics", "mmx_eval_reward", "mmx_kernel_timing", "mmx_kernel_times", "mmx_png_encode",
-                 "mmx_png_pack", "mmx_image_stats", "mmx_queue_init", "mmx_queue_advance", "mmx_set_step_rows", "mmx_set_step_order",
-                 "mmx_set_render_effects", "mmx_rollout_actions", "mmx_rollout_expert_record", "mmx_snapshot", "mmx_restore"):
-        getattr(L, name).restype = C.c_int
+    for name, (restype, argtypes) in _PROTOS.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 

@@ -1,8 +1,6 @@
-// C-ABI implementation (include/mmx_api.h, include/mmx_tuning.h): device allocation, host-side seeding, launches.
-//
-// Host-side seeding restates numpy's SeedSequence / PCG64 initialisation (the reference seeds
-// every episode through gymnasium: Generator(PCG64(SeedSequence(seed))), gym_env.py:491) so the
-// device PCG64 streams are bit-identical to the reference's np_random streams.
+// C-ABI implementation (include/mmx_api.h, include/mmx_tuning.h): device allocation, launches.  The kernel
+// sources' launchers come from mmx_launch.h; the host-only parts are headers of their own: the seeding
+// (mmx_seed.h) and the rollout's launch plan (mmx_plan.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,46 +13,12 @@
 
 #include "../../include/mmx_api.h"
 #include "../../include/mmx_tuning.h"
+#include "mmx_launch.h"
+#include "mmx_plan.h"
+#include "mmx_seed.h"
 #include "mmx_state.h"
 
-extern "C" hipError_t mmx_launch_reset(const MMXState* S, const unsigned char* mask, const int* task, hipStream_t st);
-extern "C" hipError_t mmx_launch_step(const MMXState* S, const float* action, int adim, int expert_autoreset,
-                                      int base, int count, int nsteps, hipStream_t st, const int* order);
-extern "C" hipError_t mmx_launch_step_l192(const MMXState* S, const float* action, int adim, int expert_autoreset,
-                                           int base, int count, int nsteps, hipStream_t st, const int* order);
-extern "C" hipError_t mmx_launch_traj(const MMXState* S, const MMXTraj* R, const float* actions, int adim, int expert,
-                                      int base, int count, int nsteps, int k0, hipStream_t st, const int* order);
-extern "C" hipError_t mmx_launch_traj_l192(const MMXState* S, const MMXTraj* R, const float* actions, int adim, int expert,
-                                           int base, int count, int nsteps, int k0, hipStream_t st, const int* order);
-extern "C" hipError_t mmx_launch_order(const MMXState* S, int base, int count, int* order, int threads, hipStream_t st);
-extern "C" hipError_t mmx_launch_expert(const MMXState* S, int n, float* action, hipStream_t st);
-extern "C" hipError_t mmx_launch_physics(const MMXState* S, int n, int with_ik, hipStream_t st);
-extern "C" hipError_t mmx_launch_physics_l192(const MMXState* S, int n, int with_ik, hipStream_t st);
-extern "C" hipError_t mmx_launch_forward(const MMXState* S, hipStream_t st);
-extern "C" hipError_t mmx_launch_render(const MMXState* S, int base, int count, hipStream_t st);
-extern "C" hipError_t mmx_launch_render_bg(const MMXState* S, hipStream_t st);
-extern "C" hipError_t mmx_launch_render_masked(const MMXState* S, int base, int count, const unsigned char* mask,
-                                               hipStream_t st);
-extern "C" void mmx_render_effects_bind(const MMXState* S, int flags, unsigned short* shmap);
-extern "C" size_t mmx_render_shadow_map_bytes();
-extern "C" hipError_t mmx_launch_queue(const MMXState* S, int* slot, int* next, int n_ep, const unsigned long long* rng,
-                                       const int* qtask, unsigned char* mask, int* task, int* slot_out, int* fin_out,
-                                       hipStream_t st);
-extern "C" hipError_t mmx_launch_png(const uint8_t* rgb, int64_t img_stride, int n, int W, int H, uint8_t* out,
-                                     int64_t out_stride, int32_t* sizes, uint32_t* scratch, hipStream_t st);
-extern "C" hipError_t mmx_launch_png_pack(const uint8_t* out, int64_t out_stride, const int32_t* sizes,
-                                          const int64_t* offsets, int n, uint8_t* packed, hipStream_t st);
-extern "C" hipError_t mmx_launch_image_stats(const uint8_t* rgb, int64_t img_stride, int n, int64_t npx, int64_t* out,
-                                             hipStream_t st);
-extern "C" int64_t mmx_png_bound_bytes(int width, int height);
-extern "C" int64_t mmx_png_scratch_bytes(int width, int height);
-extern "C" int64_t mmx_snapshot_record_bytes(int cameras);
-extern "C" hipError_t mmx_launch_snapshot(const MMXState* S, void* blob, hipStream_t st);
-extern "C" hipError_t mmx_launch_restore(const MMXState* S, const void* blob, int n_records, const int* src,
-                                         unsigned char* mask, hipStream_t st);
-extern "C" hipError_t mmx_launch_expert_physics(const MMXState* S, int n, hipStream_t st);
-extern "C" hipError_t mmx_launch_reward(const MMXState* S, const float* obj, const float* ee, const float* ctrl7,
-                                        const int* pairs, int max_pairs, hipStream_t st);
+using namespace mmx_host;
 
 struct mmx_sim {
   MMXState S;
@@ -62,14 +26,16 @@ struct mmx_sim {
   hipStream_t stream;
   std::string err;
   std::vector<void*> allocs;
+  // a dalloc of this sim has failed: read by mmx_create alone, once, after its allocations (later callers of
+  // dalloc, mmx_queue_init and mmx_set_render_effects, test the pointer they get; the flag then only stays set)
+  bool alloc_failed = false;
   float* expert_action;  // [N][4]
   unsigned char* d_mask;
   int* d_task;
   int* d_order;  // [N] dispatch order of the rollout's step launches (MMX_STEP_ORDER)
   // Multi-step rollouts split the envs into `nlanes` independent ranges, each stepped on its own
   // stream (lane 0 = the caller's stream): the ranges never wait for each other between steps,
-  // so one range's last-wave tail overlaps the next step of the others.
-  static constexpr int kMaxLanes = 8;
+  // so one range's last-wave tail overlaps the next step of the others (at most kMaxLanes, mmx_plan.h).
   int nlanes = 1;
   // cap on the env steps per mmx_env_step_kernel launch in expert rollouts without cameras (MMX_FUSE
   // overrides): with the staggered lanes 32 beat 16 by 0.5 % and 8 lost 2.7 % on 512-step C3 windows
@@ -92,7 +58,7 @@ struct mmx_sim {
   hipStream_t rstream = nullptr;
   hipEvent_t ev_step = nullptr, ev_rend[2] = {};
   // opt-in render effects (mmx_set_render_effects): the flags and the per-env shadow height maps
-  // (allocated when shadows are first asked for); mmx_render.hip keeps them under S.images
+  // (allocated when shadows are first asked for), passed to every render launch (render() below)
   int render_effects = 0;
   unsigned short* shmap = nullptr;
   // per-launch kernel timing (mmx_kernel_timing): an event pair around every step / render launch
@@ -111,72 +77,6 @@ struct mmx_sim {
 };
 
 namespace {
-
-// ---------------------------------------------------------------- numpy SeedSequence / PCG64
-constexpr uint32_t kInitA = 0x43b0d7e5u, kMultA = 0x931e8875u, kInitB = 0x8b51f9ddu, kMultB = 0x58f38dedu;
-constexpr uint32_t kMixL = 0xca01f9ddu, kMixR = 0x4973f715u;
-
-uint32_t hashmix(uint32_t v, uint32_t& hc) {
-  v ^= hc;
-  hc *= kMultA;
-  v *= hc;
-  v ^= v >> 16;
-  return v;
-}
-uint32_t mix(uint32_t x, uint32_t y) {
-  uint32_t r = kMixL * x - kMixR * y;
-  return r ^ (r >> 16);
-}
-std::vector<uint32_t> seed_words(uint64_t s) {
-  std::vector<uint32_t> w{static_cast<uint32_t>(s)};
-  if (s >> 32) w.push_back(static_cast<uint32_t>(s >> 32));
-  return w;
-}
-// SeedSequence(entropy, spawn_key).generate_state(n_out, uint32)
-std::vector<uint32_t> seedseq(std::vector<uint32_t> ent, const std::vector<uint32_t>& spawn, int n_out) {
-  if (!spawn.empty() && ent.size() < 4) ent.resize(4, 0u);
-  ent.insert(ent.end(), spawn.begin(), spawn.end());
-  uint32_t pool[4];
-  uint32_t hc = kInitA;
-  for (int i = 0; i < 4; i++) pool[i] = hashmix(i < static_cast<int>(ent.size()) ? ent[i] : 0u, hc);
-  for (int s = 0; s < 4; s++)
-    for (int d = 0; d < 4; d++)
-      if (s != d) pool[d] = mix(pool[d], hashmix(pool[s], hc));
-  for (size_t s = 4; s < ent.size(); s++)
-    for (int d = 0; d < 4; d++) pool[d] = mix(pool[d], hashmix(ent[s], hc));
-  std::vector<uint32_t> out(n_out);
-  uint32_t hb = kInitB;
-  for (int i = 0; i < n_out; i++) {
-    uint32_t v = pool[i % 4];
-    v ^= hb;
-    hb *= kMultB;
-    v *= hb;
-    v ^= v >> 16;
-    out[i] = v;
-  }
-  return out;
-}
-
-using u128 = unsigned __int128;
-const u128 kPcgMult = (static_cast<u128>(0x2360ED051FC65DA4ull) << 64) | 0x4385DF649FCCF645ull;
-
-// PCG64(SeedSequence(seed)) initial (state, inc)
-void pcg64_seed(uint64_t seed, uint64_t out[4]) {
-  std::vector<uint32_t> st = seedseq(seed_words(seed), {}, 8);
-  uint64_t v[4];
-  for (int i = 0; i < 4; i++) v[i] = static_cast<uint64_t>(st[2 * i]) | (static_cast<uint64_t>(st[2 * i + 1]) << 32);
-  u128 initstate = (static_cast<u128>(v[0]) << 64) | v[1];
-  u128 initseq = (static_cast<u128>(v[2]) << 64) | v[3];
-  u128 inc = (initseq << 1) | 1;
-  u128 s = 0;
-  s = s * kPcgMult + inc;
-  s += initstate;
-  s = s * kPcgMult + inc;
-  out[0] = static_cast<uint64_t>(s >> 64);
-  out[1] = static_cast<uint64_t>(s);
-  out[2] = static_cast<uint64_t>(inc >> 64);
-  out[3] = static_cast<uint64_t>(inc);
-}
 
 // Makes the sim's device current for the duration of an entry point (NULL-stream launches and
 // hipMemcpy go to the current device) and restores the caller's device afterwards.
@@ -217,14 +117,24 @@ int check_fault(mmx_sim* sim, const char* what) {
 template <typename T>
 T* dalloc(mmx_sim* sim, size_t count) {
   void* p = nullptr;
-  if (hipMalloc(&p, count * sizeof(T)) != hipSuccess) return nullptr;
-  if (hipMemset(p, 0, count * sizeof(T)) != hipSuccess) {
+  if (hipMalloc(&p, count * sizeof(T)) != hipSuccess) p = nullptr;
+  if (p && hipMemset(p, 0, count * sizeof(T)) != hipSuccess) {
     (void)hipFree(p);
-    return nullptr;
+    p = nullptr;
   }
-  sim->allocs.push_back(p);
+  if (p)
+    sim->allocs.push_back(p);
+  else
+    sim->alloc_failed = true;
   return static_cast<T*>(p);
 }
+// the render of envs [base, base + count) of `S` (the sim's state, or the overlap branch's copy of it with
+// the other pose buffer) with the sim's effects; mask: device bytes, null = every env
+hipError_t render(const mmx_sim* sim, const MMXState& S, int base, int count, const unsigned char* mask, hipStream_t st) {
+  return mmx_launch_render(&S, base, count, mask, sim->render_effects, sim->shmap, st);
+}
+// a task code of mmx_reset's task_override / mmx_queue_init's tasks: negative (none) or obj << 4 | bin
+bool task_code_ok(int t) { return t < 0 || ((t >> 4) <= 2 && (t & 15) <= 2); }
 
 }  // namespace
 
@@ -353,23 +263,14 @@ int mmx_create(const mmx_config* cfg, mmx_sim** out) {
     const size_t sg = static_cast<size_t>((cfg->image_size + 15) & ~15);
     S.bg_overhead = dalloc<unsigned int>(sim, sg * sg);
   }
-  for (void* p : sim->allocs)
-    if (!p) {
-      mmx_destroy(sim);
-      return MMX_ENOMEM;
-    }
-  if (!S.qpos || !S.con || !S.efc_ovf || !S.fault || !sim->d_task || !sim->d_order) {
+  if (sim->alloc_failed) {  // any of the buffers above
     mmx_destroy(sim);
     return MMX_ENOMEM;
   }
   // gymnasium's lazily created np_random uses OS entropy when never seeded
   std::random_device rd;
   std::vector<unsigned long long> rng(4 * n);
-  for (size_t i = 0; i < n; i++) {
-    uint64_t st[4];
-    pcg64_seed((static_cast<uint64_t>(rd()) << 32) ^ rd(), st);
-    for (int k = 0; k < 4; k++) rng[4 * i + k] = st[k];
-  }
+  for (size_t i = 0; i < n; i++) pcg64_seed_row(&rng[4 * i], (static_cast<uint64_t>(rd()) << 32) ^ rd());
   if (hipMemcpy(S.rng, rng.data(), rng.size() * sizeof(unsigned long long), hipMemcpyHostToDevice) != hipSuccess) {
     mmx_destroy(sim);
     return MMX_EDEVICE;
@@ -392,7 +293,7 @@ int mmx_create(const mmx_config* cfg, mmx_sim** out) {
   }
   sim->step_order = 1;
   if (const char* v = std::getenv("MMX_STEP_ORDER")) sim->step_order = std::atoi(v) != 0;
-  lanes = std::max(1, std::min(lanes, std::min(N, int(mmx_sim::kMaxLanes))));
+  lanes = std::max(1, std::min(lanes, std::min(N, int(kMaxLanes))));
   if (hipEventCreateWithFlags(&sim->ev_fork, hipEventDisableTiming) != hipSuccess) lanes = 1;
   for (int l = 1; l < lanes; l++)
     if (hipStreamCreateWithFlags(&sim->lane[l], hipStreamNonBlocking) != hipSuccess ||
@@ -425,7 +326,6 @@ void mmx_destroy(mmx_sim* sim) {
   if (!sim) return;
   DeviceGuard guard(sim);
   (void)hipDeviceSynchronize();
-  if (sim->render_effects) mmx_render_effects_bind(&sim->S, 0, nullptr);
   for (void* p : sim->allocs)
     if (p) (void)hipFree(p);
   for (int l = 1; l < sim->nlanes; l++) {
@@ -460,9 +360,7 @@ int mmx_reset(mmx_sim* sim, const uint64_t* seeds, const uint8_t* seed_given, co
     for (size_t i = 0; i < n; i++) {
       if (env_mask && !env_mask[i]) continue;
       if (seed_given && !seed_given[i]) continue;
-      uint64_t st[4];
-      pcg64_seed(seeds[i], st);
-      for (int k = 0; k < 4; k++) rng[4 * i + k] = st[k];
+      pcg64_seed_row(&rng[4 * i], seeds[i]);
       epi[EPI_N * i + EPI_RNG_HAS32] = 0;
     }
     if (hipMemcpy(S.rng, rng.data(), rng.size() * sizeof(unsigned long long), hipMemcpyHostToDevice) != hipSuccess ||
@@ -477,17 +375,15 @@ int mmx_reset(mmx_sim* sim, const uint64_t* seeds, const uint8_t* seed_given, co
     dmask = sim->d_mask;
   }
   if (task_override) {
-    for (size_t i = 0; i < n; i++) {
-      const int t = task_override[i];
-      if (t >= 0 && ((t >> 4) > 2 || (t & 15) > 2)) return fail(sim, MMX_EINVAL, "task_override out of range");
-    }
+    for (size_t i = 0; i < n; i++)
+      if (!task_code_ok(task_override[i])) return fail(sim, MMX_EINVAL, "task_override out of range");
     if (hipMemcpyAsync(sim->d_task, task_override, n * sizeof(int), hipMemcpyHostToDevice, sim->stream) != hipSuccess)
       return fail(sim, MMX_EDEVICE, "task upload");
     dtask = sim->d_task;
   }
   int rc = hip_check(sim, mmx_launch_reset(&S, dmask, dtask, sim->stream), "mmx_reset");
   if (rc) return rc;
-  rc = hip_check(sim, mmx_launch_render(&S, 0, S.N, sim->stream), "mmx_reset render");
+  rc = hip_check(sim, render(sim, S, 0, S.N, nullptr, sim->stream), "mmx_reset render");
   if (rc) return rc;
   rc = hip_check(sim, hipStreamSynchronize(sim->stream), "mmx_reset sync");
   return rc ? rc : check_fault(sim, "mmx_reset");
@@ -531,7 +427,7 @@ int mmx_step(mmx_sim* sim, const float* action_dev, int32_t action_dim) {
   int* ord = sim->step_order ? sim->d_order : nullptr;
   hipError_t e = ord ? mmx_launch_order(&sim->S, 0, sim->S.N, ord, 1024, sim->stream) : hipSuccess;
   if (e == hipSuccess) e = step_launchers(sim).step(&sim->S, action_dev, action_dim, 0, 0, sim->S.N, 1, sim->stream, ord);
-  if (e == hipSuccess) e = mmx_launch_render(&sim->S, 0, sim->S.N, sim->stream);
+  if (e == hipSuccess) e = render(sim, sim->S, 0, sim->S.N, nullptr, sim->stream);
   return hip_check(sim, e, "mmx_step");
 }
 
@@ -582,71 +478,10 @@ int mmx_kernel_times(mmx_sim* sim, float* step_ms, int32_t* step_launches, float
   return hip_check(sim, e, "mmx_kernel_times");
 }
 
-// Launch plan of an n-step expert rollout without cameras.  A launch runs `len` consecutive env steps
-// of its lane's envs, len = min(fuse, ceil(n / 4)); lane l of L starts with a launch of l * len / L
-// steps (none for lane 0), then launches of len, then the remainder, so the lanes' launch boundaries
-// are spread over the launch period instead of falling together.  Every launch ends with a drain (its
-// slowest workgroups finish while its slots empty); the other lanes fill the slots it frees as long as
-// they are not draining at the same time.  Measured on the driver's 20-step windows
-// (tools/sweep_env.py, profiles/r06_sweep_driver_plans.json): equal 3-step launches, all lanes in step,
-// 2.72 M env steps/s; the staggered 5-step plan 2.87 M (+5.4 %); staggered 3-, 4-, 6-, 7-, 10-step
-// plans and 1-step final launches between them; 512-step windows +0.5 % (16-step launches offset by 4).
-// With cameras every step is rendered: one step per launch, one lane.
-static int rollout_len(const mmx_sim* sim, int n) {
-  if (sim->S.image_size > 0) return 1;
-  return std::max(1, std::min(sim->fuse, (n + 3) / 4));
-}
-// lanes of a rollout: with cameras one (every step ends in the render over all envs, and one launch
-// orders all envs longest-first: C5 +2.0 % over 4 lanes)
-static int rollout_lanes(const mmx_sim* sim) { return sim->S.image_size > 0 ? 1 : sim->nlanes; }
-// Launch lengths of every lane for an n-step rollout (above): `lanes` of them (one for a single step),
-// `rounds` = the most launches any lane makes.  Env MMX_PLAN = "a,b,...[;c,d,...]" per lane (the last
-// list repeats for the lanes after it) overrides a lane's lengths for experiments when they sum to n.
-struct RolloutPlan {
-  int lanes = 0;
-  size_t rounds = 0;
-  std::vector<int> len[mmx_sim::kMaxLanes];
-};
+// The rollout's launch plan (mmx_plan.h) with the sim's lanes, fuse cap and cameras; MMX_PLAN overrides it
+static int rollout_lanes(const mmx_sim* sim) { return rollout_lanes(sim->nlanes, sim->S.image_size > 0); }
 static RolloutPlan rollout_plan(const mmx_sim* sim, int n) {
-  RolloutPlan P;
-  P.lanes = n > 1 ? rollout_lanes(sim) : 1;
-  const char* env = std::getenv("MMX_PLAN");
-  for (int lane = 0; lane < P.lanes; lane++) {
-    std::vector<int>& v = P.len[lane];
-    if (env) {
-      std::string all(env), mine;
-      size_t pos = 0;
-      for (int l = 0;; l++) {
-        const size_t sc = all.find(';', pos);
-        mine = all.substr(pos, sc == std::string::npos ? std::string::npos : sc - pos);
-        if (l == lane || sc == std::string::npos) break;
-        pos = sc + 1;
-      }
-      int sum = 0;
-      for (size_t a = 0; a < mine.size();) {
-        const int k = std::atoi(mine.c_str() + a);
-        if (k <= 0) break;
-        v.push_back(k);
-        sum += k;
-        const size_t c = mine.find(',', a);
-        if (c == std::string::npos) break;
-        a = c + 1;
-      }
-      if (sum != n) v.clear();
-    }
-    if (v.empty() && n > 0) {
-      const int len = rollout_len(sim, n), L = rollout_lanes(sim);
-      int rem = n;
-      const int first = std::min(rem, lane * len / std::max(L, 1));
-      if (first > 0) {
-        v.push_back(first);
-        rem -= first;
-      }
-      for (; rem > 0; rem -= std::min(rem, len)) v.push_back(std::min(rem, len));
-    }
-    P.rounds = std::max(P.rounds, v.size());
-  }
-  return P;
+  return rollout_plan(n, sim->nlanes, sim->fuse, sim->S.image_size > 0, std::getenv("MMX_PLAN"));
 }
 int mmx_rollout_launches(const mmx_sim* sim, int32_t n_env_steps) {
   return sim ? (int)rollout_plan(sim, n_env_steps).rounds : 0;
@@ -677,7 +512,7 @@ static int rollout(mmx_sim* sim, int n, const char* what, Launch launch) {
       if (e == hipSuccess) e = timed(sim, sim->stream, sim->t_step, [&] { return launch(&Sk, 0, N, 1, k, sim->stream, ord); });
       if (e == hipSuccess) e = hipEventRecord(sim->ev_step, sim->stream);
       if (e == hipSuccess) e = hipStreamWaitEvent(rs, sim->ev_step, 0);
-      if (e == hipSuccess) e = timed(sim, rs, sim->t_render, [&] { return mmx_launch_render(&Sk, 0, N, rs); });
+      if (e == hipSuccess) e = timed(sim, rs, sim->t_render, [&] { return render(sim, Sk, 0, N, nullptr, rs); });
       if (e == hipSuccess) e = hipEventRecord(sim->ev_rend[k & 1], rs);
     }
     // the caller's stream sees the last render; S.rpose names the newest poses
@@ -694,7 +529,7 @@ static int rollout(mmx_sim* sim, int n, const char* what, Launch launch) {
     e = hipEventRecord(sim->ev_fork, sim->stream);
     for (int l = 1; l < L && e == hipSuccess; l++) e = hipStreamWaitEvent(sim->lane[l], sim->ev_fork, 0);
   }
-  int k0[mmx_sim::kMaxLanes] = {};  // the rollout step each lane's next launch starts at
+  int k0[kMaxLanes] = {};  // the rollout step each lane's next launch starts at
   // with cameras (L = 1): the step of all envs, then ONE render launch over all envs (the render's
   // 80 KB workgroups cannot share a CU with the step kernel's: a render per lane beside the other
   // lanes' steps ran as a trickle, C5 -2.8 %)
@@ -710,7 +545,7 @@ static int rollout(mmx_sim* sim, int n, const char* what, Launch launch) {
       k0[l] += ns;
     }
     if (e == hipSuccess && sim->S.image_size > 0)
-      e = timed(sim, sim->stream, sim->t_render, [&] { return mmx_launch_render(&sim->S, 0, N, sim->stream); });
+      e = timed(sim, sim->stream, sim->t_render, [&] { return render(sim, sim->S, 0, N, nullptr, sim->stream); });
   }
   if (L > 1)  // join: the caller's stream sees the whole rollout, as with a single launch chain
     for (int l = 1; l < L; l++) {
@@ -847,7 +682,7 @@ int mmx_forward(mmx_sim* sim) {
   if (!sim) return MMX_EINVAL;
   DeviceGuard guard(sim);
   hipError_t e = mmx_launch_forward(&sim->S, sim->stream);
-  if (e == hipSuccess) e = mmx_launch_render(&sim->S, 0, sim->S.N, sim->stream);
+  if (e == hipSuccess) e = render(sim, sim->S, 0, sim->S.N, nullptr, sim->stream);
   return hip_check(sim, e, "mmx_forward");
 }
 
@@ -862,7 +697,6 @@ int mmx_set_render_effects(mmx_sim* sim, int32_t flags) {
     if (!sim->shmap) return fail(sim, MMX_ENOMEM, "mmx_set_render_effects: shadow maps");
   }
   sim->render_effects = flags;
-  mmx_render_effects_bind(&sim->S, flags, sim->shmap);
   return MMX_OK;
 }
 int mmx_get_render_effects(const mmx_sim* sim) { return sim ? sim->render_effects : 0; }
@@ -945,7 +779,7 @@ int mmx_restore(mmx_sim* sim, const void* snap_dev, int64_t rec_bytes, int32_t n
   unsigned char* mask = S.image_size > 0 ? sim->d_mask : nullptr;
   hipError_t e = mmx_launch_restore(&S, snap_dev, n_records, src_dev, mask, sim->stream);
   // the restored envs' images and segment ids, redrawn from the restored poses with the sim's current effects
-  if (e == hipSuccess && mask) e = mmx_launch_render_masked(&S, 0, S.N, mask, sim->stream);
+  if (e == hipSuccess && mask) e = render(sim, S, 0, S.N, mask, sim->stream);
   return hip_check(sim, e, "mmx_restore");
 }
 
@@ -953,10 +787,8 @@ int mmx_queue_init(mmx_sim* sim, int32_t n_episodes, const uint64_t* seeds, cons
   if (!sim || n_episodes < 0 || (n_episodes > 0 && !tasks)) return MMX_EINVAL;
   DeviceGuard guard(sim);
   const size_t E = static_cast<size_t>(n_episodes), n = static_cast<size_t>(sim->S.N);
-  for (size_t e = 0; e < E; e++) {
-    const int t = tasks[e];
-    if (t >= 0 && ((t >> 4) > 2 || (t & 15) > 2)) return fail(sim, MMX_EINVAL, "queue task out of range");
-  }
+  for (size_t e = 0; e < E; e++)
+    if (!task_code_ok(tasks[e])) return fail(sim, MMX_EINVAL, "queue task out of range");
   if (hipStreamSynchronize(sim->stream) != hipSuccess) return fail(sim, MMX_EDEVICE, "mmx_queue_init sync");
   for (void* p : {static_cast<void*>(sim->q_slot), static_cast<void*>(sim->q_next), static_cast<void*>(sim->q_task),
                   static_cast<void*>(sim->q_rng)}) {
@@ -975,11 +807,7 @@ int mmx_queue_init(mmx_sim* sim, int32_t n_episodes, const uint64_t* seeds, cons
   if (e == hipSuccess && E) e = hipMemcpy(sim->q_task, tasks, E * sizeof(int), hipMemcpyHostToDevice);
   if (e == hipSuccess && seeds && E) {  // PCG64(SeedSequence(seed_e)) of every episode, once
     std::vector<unsigned long long> rng(4 * E);
-    for (size_t k = 0; k < E; k++) {
-      uint64_t st[4];
-      pcg64_seed(seeds[k], st);
-      for (int j = 0; j < 4; j++) rng[4 * k + j] = st[j];
-    }
+    for (size_t k = 0; k < E; k++) pcg64_seed_row(&rng[4 * k], seeds[k]);
     sim->q_rng = dalloc<unsigned long long>(sim, 4 * E);
     if (!sim->q_rng) return fail(sim, MMX_EDEVICE, "queue allocation");
     e = hipMemcpy(sim->q_rng, rng.data(), rng.size() * sizeof(unsigned long long), hipMemcpyHostToDevice);
@@ -997,12 +825,12 @@ int mmx_queue_advance(mmx_sim* sim, int32_t* slot_ep_dev, int32_t* fin_ep_dev) {
   hipError_t e = mmx_launch_queue(&S, sim->q_slot, sim->q_next, sim->q_n, sim->q_rng, sim->q_task, sim->d_mask,
                                   sim->d_task, slot_ep_dev, fin_ep_dev, sim->stream);
   if (e == hipSuccess) e = mmx_launch_reset(&S, sim->d_mask, sim->d_task, sim->stream);
-  if (e == hipSuccess) e = mmx_launch_render_masked(&S, 0, S.N, sim->d_mask, sim->stream);
+  if (e == hipSuccess) e = render(sim, S, 0, S.N, sim->d_mask, sim->stream);
   return hip_check(sim, e, "mmx_queue_advance");
 }
 
 uint32_t mmx_episode_seed(uint64_t root, int32_t index) {
-  return seedseq(seed_words(root), {static_cast<uint32_t>(index)}, 1)[0];
+  return episode_seed(root, index);
 }
 
 }  // extern "C"

@@ -1,0 +1,65 @@
+// The host seam between mmx_api.cpp and the kernel sources: every non-kernel extern "C" function that one
+// source defines and another calls, declared once.  mmx_api.cpp includes it and so does every source that
+// defines one of them (mmx_step.inc, mmx_render.hip, mmx_png.hip, mmx_snapshot.hip), so a parameter list
+// changed on one side only is a compile error.  (The diagnostic exports that tools load through ctypes,
+// mmx_fsm_profile and mmx_render_clock among them, are not called across sources and are not listed.)
+#ifndef MMX_LAUNCH_H
+#define MMX_LAUNCH_H
+#include <hip/hip_runtime.h>
+
+#include "mmx_state.h"
+
+extern "C" {
+
+// mmx_step.inc, built once per LDS-row layout: the launchers' names carry the layout's suffix
+#define MMX_DECLARE_STEP_LAUNCHERS(sfx)                                                                                \
+  hipError_t mmx_launch_step##sfx(const MMXState* S, const float* action, int adim, int expert, int base, int count,   \
+                                  int nsteps, hipStream_t st, const int* order);                                       \
+  hipError_t mmx_launch_traj##sfx(const MMXState* S, const MMXTraj* R, const float* actions, int adim, int expert,     \
+                                  int base, int count, int nsteps, int k0, hipStream_t st, const int* order);          \
+  hipError_t mmx_launch_physics##sfx(const MMXState* S, int n, int with_ik, hipStream_t st);
+MMX_DECLARE_STEP_LAUNCHERS()
+MMX_DECLARE_STEP_LAUNCHERS(_l192)
+#undef MMX_DECLARE_STEP_LAUNCHERS
+
+// mmx_kernels.hip
+hipError_t mmx_launch_order(const MMXState* S, int base, int count, int* order, int threads, hipStream_t st);
+hipError_t mmx_launch_queue(const MMXState* S, int* slot, int* next, int n_ep, const unsigned long long* rng,
+                            const int* qtask, unsigned char* mask, int* task, int* slot_out, int* fin_out, hipStream_t st);
+hipError_t mmx_launch_reset(const MMXState* S, const unsigned char* mask, const int* task, hipStream_t st);
+hipError_t mmx_launch_expert(const MMXState* S, int n, float* action, hipStream_t st);
+hipError_t mmx_launch_expert_physics(const MMXState* S, int n, hipStream_t st);
+hipError_t mmx_launch_reward(const MMXState* S, const float* obj, const float* ee, const float* ctrl7, const int* pairs,
+                             int max_pairs, hipStream_t st);
+hipError_t mmx_launch_forward(const MMXState* S, hipStream_t st);
+
+// mmx_render.hip; mmx_launch_render_lit, mmx_render_shadow_map_bytes: its second build, mmx_render_lit.hip.
+// The render of envs [base, base + count), with a device mask (N bytes; may be null) only of the envs whose
+// byte is set; flags = the sim's MMX_RENDER_* effects (0: the flat kernel, else mmx_launch_render_lit),
+// shmap = its shadow maps (null without MMX_RENDER_SHADOWS)
+hipError_t mmx_launch_render(const MMXState* S, int base, int count, const unsigned char* mask, int flags,
+                             unsigned short* shmap, hipStream_t st);
+hipError_t mmx_launch_render_lit(const MMXState* S, int base, int count, const unsigned char* mask, int flags,
+                                 unsigned short* shmap, hipStream_t st);
+hipError_t mmx_launch_render_bg(const MMXState* S, hipStream_t st);
+size_t mmx_render_lds_bytes();
+size_t mmx_render_shadow_map_bytes();
+
+// mmx_png.hip
+hipError_t mmx_launch_png(const uint8_t* rgb, int64_t img_stride, int n, int W, int H, uint8_t* out, int64_t out_stride,
+                          int32_t* sizes, uint32_t* scratch, hipStream_t st);
+hipError_t mmx_launch_png_pack(const uint8_t* out, int64_t out_stride, const int32_t* sizes, const int64_t* offsets, int n,
+                               uint8_t* packed, hipStream_t st);
+hipError_t mmx_launch_image_stats(const uint8_t* rgb, int64_t img_stride, int n, int64_t npx, int64_t* out, hipStream_t st);
+int64_t mmx_png_bound_bytes(int width, int height);
+int64_t mmx_png_scratch_bytes(int width, int height);
+
+// mmx_snapshot.hip
+hipError_t mmx_launch_snapshot(const MMXState* S, void* blob, hipStream_t st);
+hipError_t mmx_launch_restore(const MMXState* S, const void* blob, int n_records, const int* src, unsigned char* mask,
+                              hipStream_t st);
+int64_t mmx_snapshot_record_bytes(int cameras);
+
+}  // extern "C"
+
+#endif

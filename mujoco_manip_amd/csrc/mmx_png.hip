@@ -19,6 +19,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mmx_launch.h"
+
 #define PNG_WG 256
 static constexpr int kChunk = 512;  // IDAT data bytes per chunk (12 bytes of framing each)
 static constexpr int kMaxMatch = 258;

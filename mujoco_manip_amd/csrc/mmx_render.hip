@@ -31,9 +31,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <atomic>
-#include <mutex>
-#include <vector>
 #ifndef MMR_LIT
 #define MMR_LIT 0
 #endif
@@ -44,6 +41,7 @@
 #include "mmx_render_gen.h"
 #include "mmx_device.h"
 #include "mmx_state.h"
+#include "mmx_launch.h"
 
 #ifndef MMR_WG
 #define MMR_WG 512
@@ -859,51 +857,18 @@ extern "C" size_t mmx_render_lds_bytes() {
          sizeof(float) * 8 * MMR_NMAT + sizeof(unsigned short) * kBPW * MMR_NTRI + sizeof(RTri) * kBigCache;
 }
 
-// Opt-in render effects per sim (mmx_set_render_effects).  MMXState is the step kernels' argument too and
-// stays as it is, so the flags and the shadow map of a sim are kept here, under the sim's image buffer
-// (one per sim for its lifetime; the pose double buffering of camera rollouts copies the state but
-// shares it).  mmx_destroy unbinds.  No sim has asked for an effect: no lookup.
-extern "C" hipError_t mmx_launch_render_lit(const MMXState* S, int base, int count, const unsigned char* mask,
-                                            hipStream_t st, int flags, unsigned short* shmap);
-namespace {
-struct RendFx {
-  const unsigned char* images;
-  int flags;
-  unsigned short* shmap;
-};
-std::mutex g_fx_mu;
-std::vector<RendFx> g_fx;
-std::atomic<int> g_fx_n{0};
-}  // namespace
-extern "C" void mmx_render_effects_bind(const MMXState* S, int flags, unsigned short* shmap) {
-  std::lock_guard<std::mutex> lock(g_fx_mu);
-  for (size_t k = 0; k < g_fx.size(); k++)
-    if (g_fx[k].images == S->images) g_fx.erase(g_fx.begin() + k--);
-  if (flags) g_fx.push_back(RendFx{S->images, flags, shmap});
-  g_fx_n.store((int)g_fx.size(), std::memory_order_release);
-}
-
-// envs [base, base + count); with a device mask (N bytes) only the envs whose byte is set
-extern "C" hipError_t mmx_launch_render_masked(const MMXState* S, int base, int count, const unsigned char* mask,
-                                               hipStream_t st) {
+// envs [base, base + count); with a device mask (N bytes) only the envs whose byte is set.  flags and shmap:
+// the sim's opt-in effects (mmx_set_render_effects) and shadow maps, passed by the caller with every launch
+// (MMXState is the step kernels' argument too and stays as it is); no flag set: the flat kernel
+extern "C" hipError_t mmx_launch_render(const MMXState* S, int base, int count, const unsigned char* mask, int flags,
+                                        unsigned short* shmap, hipStream_t st) {
   if (count <= 0 || S->image_size <= 0) return hipSuccess;
-  if (g_fx_n.load(std::memory_order_acquire)) {
-    RendFx fx{nullptr, 0, nullptr};
-    {
-      std::lock_guard<std::mutex> lock(g_fx_mu);
-      for (const RendFx& e : g_fx)
-        if (e.images == S->images) fx = e;
-    }
-    if (fx.flags) return mmx_launch_render_lit(S, base, count, mask, st, fx.flags, fx.shmap);
-  }
+  if (flags) return mmx_launch_render_lit(S, base, count, mask, flags, shmap, st);
   const int rows = rend_band_rows((S->image_size + 15) & ~15);
   const int bands = (S->image_size + rows - 1) / rows;
   hipLaunchKernelGGL(mmx_render_kernel, dim3((bands + kBPW - 1) / kBPW, 2, count), dim3(RWG), mmx_render_lds_bytes(), st, *S,
                      base, mask);
   return hipGetLastError();
-}
-extern "C" hipError_t mmx_launch_render(const MMXState* S, int base, int count, hipStream_t st) {
-  return mmx_launch_render_masked(S, base, count, nullptr, st);
 }
 #else  // MMR_LIT
 
@@ -1064,8 +1029,8 @@ static_assert(kShN % kShBandRows == 0 && (kShBandRows * kShN) % 4 == 0, "whole b
 
 // the render of envs [base, base + count) with effects: the shadow pass (when asked for) on the same
 // stream, pose buffer and env mask, then the lit kernel
-extern "C" hipError_t mmx_launch_render_lit(const MMXState* S, int base, int count, const unsigned char* mask,
-                                            hipStream_t st, int flags, unsigned short* shmap) {
+extern "C" hipError_t mmx_launch_render_lit(const MMXState* S, int base, int count, const unsigned char* mask, int flags,
+                                            unsigned short* shmap, hipStream_t st) {
   if (count <= 0 || S->image_size <= 0) return hipSuccess;
   if ((flags & kFxShadows) && !shmap) return hipErrorInvalidValue;
   static const hipError_t attr = [] {  // dynamic LDS past the default limit, once

@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "mmx_state.h"
+#include "mmx_launch.h"
 
 namespace {
 

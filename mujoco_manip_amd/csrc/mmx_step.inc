@@ -37,6 +37,7 @@
 #include "mmx_clock.h"
 #include "mmx_geom.h"
 #include "mmx_state.h"
+#include "mmx_launch.h"
 
 #define WG 64  // lanes of the wave that runs a phase
 // lane within the wave (a workgroup is one wave: one env)

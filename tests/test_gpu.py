@@ -11,6 +11,7 @@ The oracle is the checker only; every value under test comes out of the HIP kern
 """
 import numpy as np
 import pytest
+from rollout_plan_ref import plan_launches as _plan_launches
 
 pytestmark = pytest.mark.gpu
 
@@ -478,17 +479,6 @@ def test_rollout_lanes_bit_identical(monkeypatch):
         q, v, _, _ = env.sim.get_state()
         outs.append(np.concatenate([q, v, env.sim.view("episode_i", _lib_epi_n(), "<i4").cpu().numpy()], 1))
     np.testing.assert_array_equal(outs[0], outs[1])
-
-
-def _plan_launches(n, fuse, lanes):
-    """mmx_rollout_expert's plan (mmx_api.cpp rollout_plan): len = min(fuse, ceil(n / 4)); lane l starts
-    with l * len / lanes steps, then launches of len, then the remainder; the most launches of a lane."""
-    ln = max(1, min(fuse, -(-n // 4)))
-    out = 0
-    for l in range(lanes):
-        first = min(n, l * ln // lanes)
-        out = max(out, (1 if first else 0) + -(-(n - first) // ln))
-    return out
 
 
 def test_fused_rollout_bit_identical(monkeypatch):

@@ -366,6 +366,50 @@ def test_set_render_effects_errors():
 
 
 @pytest.mark.gpu
+def test_two_live_sims_keep_their_own_effects():
+    """Every render launch gets its sim's flags and shadow maps as arguments: two live sims of the four
+    states at 64 px, A with both effects and B with none, rendered in turn (A, B, A again) give the images
+    of the sims that had the device to themselves, bit for bit; closing A leaves B's render unchanged, and
+    B set to shadows afterwards renders as a sim that had shadows from the start."""
+    torch = _need_gpu()
+    from mujoco_manip_amd import _lib
+
+    qs = _states()
+
+    def make(flags):
+        sim = _lib.Sim(len(qs), action_mode="abs_pos", image_size=64)
+        if flags is not None:
+            sim.render_effects = flags
+        sim.reset()
+        q, v, c, w = sim.get_state()
+        q[:] = qs
+        sim.set_state(q, v, c, w)
+        return sim
+
+    def images(sim):
+        sim.forward()
+        torch.cuda.synchronize()
+        rgb, seg = sim.image_views()
+        return rgb.cpu().numpy().copy(), seg.cpu().numpy().copy()
+
+    def same(got, want, msg):
+        np.testing.assert_array_equal(got[0], want[0], err_msg=msg + ": rgb")
+        np.testing.assert_array_equal(got[1], want[1], err_msg=msg + ": seg")
+
+    a, b = make(SHADOWS | TRANSLUCENT), make(None)
+    same(images(a), _render(64, SHADOWS | TRANSLUCENT), "A first")
+    same(images(b), _render(64, None), "B after A")
+    same(images(a), _render(64, SHADOWS | TRANSLUCENT), "A after B")
+    a.close()
+    same(images(b), _render(64, None), "B after A closed")
+    b.render_effects = SHADOWS
+    assert b.render_effects == SHADOWS
+    same(images(b), _render(64, SHADOWS), "B set to shadows")
+    b.close()
+    assert (_render(64, SHADOWS | TRANSLUCENT)[0] != _render(64, None)[0]).any()
+
+
+@pytest.mark.gpu
 def test_render_overlap_bit_identical_with_effects(monkeypatch):
     """MMX_RENDER_OVERLAP 0 and 1 with both effects: the shadow pass runs on the render's stream and
     pose buffer, so the images after 5 and then 2 more rollout steps are the same bit for bit."""

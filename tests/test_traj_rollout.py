@@ -372,7 +372,7 @@ def test_fused_replay_equals_loop(tmp_path):
 
 # ------------------------------------------------------------------ 8. one rollout driver
 def _lane_launches(n, fuse, lanes):
-    """Launches each lane makes for n steps (mmx_api.cpp rollout_plan, as _plan_launches in tests/test_gpu.py):
+    """Launches each lane makes for n steps (mmx_plan.h rollout_plan, as _plan_launches in tests/test_gpu.py):
     len = min(fuse, ceil(n / 4)); lane l starts with l * len / lanes steps, then launches of len, then the rest."""
     ln = max(1, min(fuse, -(-n // 4)))
     firsts = [min(n, l * ln // lanes) for l in range(lanes)]
