@@ -674,7 +674,7 @@ DEV bool epa(const GPair& GP, SVx* V, int nv, V3& nrm, float& depth, V3& pa, V3&
   static_assert(EPA_MAXF <= 128, "two faces per lane");
   const int ln = epa_lane();
   int best = -1;
-  for (int it = 0; it < 32; it++) {
+  for (;;) {  // at most EPA_MAXV - 4 expansions: each adds a vertex
     epa_sync();
     // nearest face: per lane its faces ln, ln + 64 (strict <: the lower index on ties), then the
     // wave's arg-max of -d (ties: the lowest index)
@@ -695,6 +695,8 @@ DEV bool epa(const GPair& GP, SVx* V, int nv, V3& nrm, float& depth, V3& pa, V3&
     const float fd = F[best].d;
     const SVx P = mk_sv(GP, fn);
     const float dist = dot(P.w, fn);
+    // every exit leaves `best` the nearest face of the final polytope; each pass that goes on adds one
+    // vertex (nv++ below is unconditional), so at most EPA_MAXV - 4 expansions run
     if (dist - fd < 1e-6f * (1.f + fabsf(dist)) || nv >= EPA_MAXV) break;
     // which faces P sees (lane ln: faces ln and ln + 64), the others kept in index order
     EFace f0, f1;
@@ -760,13 +762,16 @@ DEV bool epa(const GPair& GP, SVx* V, int nv, V3& nrm, float& depth, V3& pa, V3&
   epa_sync();
   if (best < 0) return false;
   const EFace& f = F[best];
+  // barycentric coordinates of the origin's projection p as signed areas about p: a face on a cylinder's
+  // side is a sliver (rim points 0.2 m apart in height, a chord of 0.2 mm wide), and the Gram determinant
+  // d00 d11 - d01^2 of such a triangle cancels to 1e-6 of its terms, which fp32 cannot hold (the witness
+  // slid up to 0.9 mm along the axis); the cross products lose only the sliver's aspect ratio
   const V3 p = f.n * f.d;
-  const V3 v0 = V[f.v(1)].w - V[f.v(0)].w, v1 = V[f.v(2)].w - V[f.v(0)].w, v2 = p - V[f.v(0)].w;
-  const float d00 = dot(v0, v0), d01 = dot(v0, v1), d11 = dot(v1, v1), d20 = dot(v2, v0), d21 = dot(v2, v1);
-  const float den = d00 * d11 - d01 * d01;
-  const float lv = den > 1e-30f ? (d11 * d20 - d01 * d21) / den : 0.f;
-  const float lw = den > 1e-30f ? (d00 * d21 - d01 * d20) / den : 0.f;
-  const float lu = 1.f - lv - lw;
+  const V3 ra = V[f.v(0)].w - p, rb = V[f.v(1)].w - p, rc = V[f.v(2)].w - p;
+  const float den = dot(cross(V[f.v(1)].w - V[f.v(0)].w, V[f.v(2)].w - V[f.v(0)].w), f.n);
+  const float lu = den > 1e-15f ? dot(cross(rb, rc), f.n) / den : 1.f;
+  const float lv = den > 1e-15f ? dot(cross(rc, ra), f.n) / den : 0.f;
+  const float lw = 1.f - lu - lv;
   pa = V[f.v(0)].a * lu + V[f.v(1)].a * lv + V[f.v(2)].a * lw;
   pb = V[f.v(0)].b * lu + V[f.v(1)].b * lv + V[f.v(2)].b * lw;
   nrm = f.n;

@@ -541,6 +541,11 @@ static int epa(const or_env* e, int g1, int g2, sv* simplex, int nsimp, double* 
     for (int q = 0; q < ne && nf < EPA_MAXF; q++)
       if (epa_make_face(V, &F[nf], edges[q][0], edges[q][1], pi)) nf++;
   }
+  /* the loop may end on its iteration count, right after an expansion compacted F: `best` then
+     indexes the array as it was before.  The answer is the closest face of the final polytope. */
+  best = -1;
+  for (int i = 0; i < nf; i++)
+    if (F[i].alive && (best < 0 || F[i].d < F[best].d)) best = i;
   if (best < 0) return 0;
   epa_face* f = &F[best];
   /* barycentric coordinates of the origin's projection on the face */

@@ -118,13 +118,17 @@ class RawModel:
         return ids[k]
 
 
-def penetration(A, B):
+def penetration(A, B, nfacets=None):
     """Exact penetration of hull(A) and hull(B) (point sets, world frame).
 
     Returns (depth, normal A->B, facets) with depth > 0 when they overlap: the origin's distance
     to the nearest facet of hull(A - B); `facets` = [(distance, normal, witness A, witness B)] of
-    all facets sorted by distance, witnesses = the barycentric combination of the facet's A and B
-    points at the origin's projection."""
+    all facets sorted by distance (the nearest `nfacets` of them when given), witnesses = the
+    barycentric combination of the facet's A and B points at the origin's projection.
+
+    Apart, depth < 0 and -depth is a lower bound of the distance (the widest facet plane between
+    the origin and the hull; the distance itself when the nearest feature is a facet), with the
+    normal a separating direction: w(n) = depth."""
     from scipy.spatial import ConvexHull
 
     A = np.asarray(A, float)
@@ -136,7 +140,7 @@ def penetration(A, B):
     dist = -h.equations[:, 3]  # outward unit normal n, n.x + off <= 0 inside: distance = -off
     order = np.argsort(dist)
     facets = []
-    for f in order:
+    for f in order[:nfacets]:
         n = h.equations[f, :3]
         tri = h.simplices[f]
         P = M[tri]
@@ -173,3 +177,295 @@ def normal_margin(facets, ang=1e-3):
         if np.dot(n, n0) < np.cos(ang):
             return d - d0
     return np.inf
+
+
+# --------------------------------------------------------------------------- support functions
+# The narrowphase sweep (tests/test_narrowphase_sweep.py) states every check through the support
+# function h(n) = max over the geom of n . x: the overlap of a pair along a unit n (A -> B) is
+# w(n) = h_A(n) + h_B(-n), they penetrate iff w(n) > 0 for every n, and the depth is min_n w(n).
+
+def geom_frame(g, pose):
+    """World centre and rotation of a box / cylinder geom (the MJCF's geoms carry no quat)."""
+    p, R = pose[g["body"]]
+    return p + R @ np.asarray(g["pos"], float), R
+
+
+def support_value(m, g, pose, n):
+    """h(n) of a collision geom: box, hull mesh (its vertices), cylinder (analytic, axis = the
+    geom frame's z: r |n_xy| + hh |n_z|), and the floor plane as the half space z <= 0 (finite
+    only along +z)."""
+    n = np.asarray(n, float)
+    if g["type"] == "plane":
+        assert n[2] > 1 - 1e-12, "the half space z <= 0 has a finite support only along +z"
+        return 0.0
+    if g["type"] == "mesh":
+        return float((m.geom_points(g, pose) @ n).max())
+    c, R = geom_frame(g, pose)
+    nl = R.T @ n
+    if g["type"] == "box":
+        return float(c @ n + np.abs(nl) @ np.asarray(g["size"], float))
+    if g["type"] == "cylinder":
+        r, hh = g["size"][:2]
+        return float(c @ n + r * np.hypot(nl[0], nl[1]) + hh * abs(nl[2]))
+    raise ValueError(g["type"])
+
+
+def overlap(m, ga, gb, pose, n):
+    """w(n) = h_A(n) + h_B(-n), n a unit vector from A to B: > 0 when the slabs along n overlap."""
+    n = np.asarray(n, float)
+    return support_value(m, ga, pose, n) + support_value(m, gb, pose, -n)
+
+
+def cylinder_points(g, pose, focus=(), coarse=96, fan=0.1):
+    """A cylinder as an inscribed prism: `coarse` sides all round and, about the azimuth of each
+    of the world directions `focus` and its opposite, sides so narrow that the prism lies
+    within r (1 - cos(delta / 2)) < 1e-8 of the cylinder there."""
+    c, R = geom_frame(g, pose)
+    r, hh = g["size"][:2]
+    az = np.linspace(0, 2 * np.pi, coarse, endpoint=False)
+    for f in focus:
+        fl = R.T @ np.asarray(f, float)
+        if np.hypot(fl[0], fl[1]) > 1e-9:
+            a0 = np.arctan2(fl[1], fl[0])
+            delta = 2 * np.sqrt(2 * 0.5e-8 / r)
+            k = int(np.ceil(fan / delta))
+            az = np.r_[az, a0 + np.arange(-k, k + 1) * delta, a0 + np.pi + np.arange(-k, k + 1) * delta]
+    ring = np.stack([r * np.cos(az), r * np.sin(az)], axis=1)
+    loc = np.concatenate([np.c_[ring, np.full(len(az), s * hh)] for s in (-1, 1)])
+    return c + loc @ R.T
+
+
+def convex_points(m, g, pose, focus=()):
+    return cylinder_points(g, pose, focus) if g["type"] == "cylinder" else m.geom_points(g, pose)
+
+
+def pair_penetration(m, ga, gb, pose, nfacets=64):
+    """Exact (depth, normal A -> B, facets) of two convex geoms.  A cylinder enters qhull as a
+    prism refined about the answer's own azimuth; its exact h then gives the depth along the
+    facet normal found, and the prism's answer (an inscribed body) bounds the exact minimum from
+    below: when the two agree within 1e-8 the depth is exact to that.  Where the refinement does
+    not settle (deep pairs whose minimiser jumps between passes) facets is None and the depth
+    only the prism's lower bound."""
+    curved = "cylinder" in (ga["type"], gb["type"])
+    d, n, fac = penetration(convex_points(m, ga, pose), convex_points(m, gb, pose), nfacets)
+    if not curved or d < 0:
+        return d, n, fac
+    focus = []
+    for _ in range(5):
+        focus.append(n)
+        d, n, fac = penetration(convex_points(m, ga, pose, focus), convex_points(m, gb, pose, focus), nfacets)
+        w = overlap(m, ga, gb, pose, n)
+        if d < 0:
+            return d, n, fac
+        if -1e-12 <= w - d < 1e-8:
+            return w, n, fac
+    return d, n, None
+
+
+def plane_penetration(m, gb, pose):
+    """The floor (z <= 0) against a convex geom: depth = -min z, normal +z (plane -> geom)."""
+    n = np.array([0.0, 0.0, 1.0])
+    return support_value(m, gb, pose, -n), n
+
+
+def box_sat(pa, Ra, ha, pb, Rb, hb):
+    """The 15 separating axes of two boxes (centre, rotation, half sizes).  Returns
+    (face overlap, face axis, edge overlap, edge axis, all six face overlaps): the smallest
+    overlap over the 6 face normals and over the 9 edge cross products, each axis a unit vector
+    signed from A to B.  Cross products shorter than 1e-6 (parallel edges) are skipped; with none
+    left the edge overlap is inf."""
+    pa, pb, ha, hb = (np.asarray(x, float) for x in (pa, pb, ha, hb))
+    d = pb - pa
+
+    def w(n):
+        return np.abs(Ra.T @ n) @ ha + np.abs(Rb.T @ n) @ hb - abs(d @ n)
+
+    def signed(n):
+        return n if d @ n >= 0 else -n
+
+    faces = [(w(R[:, k]), signed(R[:, k])) for R in (Ra, Rb) for k in range(3)]
+    face = min(faces, key=lambda t: t[0])
+    edge = (np.inf, None)
+    for i in range(3):
+        for j in range(3):
+            c = np.cross(Ra[:, i], Rb[:, j])
+            ln = np.linalg.norm(c)
+            if ln < 1e-6:
+                continue
+            c = c / ln
+            if w(c) < edge[0]:
+                edge = (w(c), signed(c))
+    return face[0], face[1], edge[0], edge[1], np.array([f[0] for f in faces])
+
+
+def box_expected_axis(face, edge):
+    """The box-box rule: an edge-edge contact only when its overlap is clearly the smaller one,
+    edge < 0.95 * face; otherwise the face axis."""
+    return "edge" if edge < 0.95 * face else "face"
+
+
+def box_edge_midpoint(pa, Ra, ha, pb, Rb, hb):
+    """The point of an edge-edge contact: the midpoint of the closest points of the two edges that
+    meet along the smallest-overlap edge axis n (A -> B), A's edge farthest along n and B's edge
+    farthest against it, each taken as its whole line."""
+    pa, pb, ha, hb = (np.asarray(x, float) for x in (pa, pb, ha, hb))
+    best = None
+    for i in range(3):
+        for j in range(3):
+            c = np.cross(Ra[:, i], Rb[:, j])
+            ln = np.linalg.norm(c)
+            if ln < 1e-6:
+                continue
+            c = c / ln if (pb - pa) @ c >= 0 else -c / ln
+            w = np.abs(Ra.T @ c) @ ha + np.abs(Rb.T @ c) @ hb - (pb - pa) @ c
+            if best is None or w < best[0]:
+                best = (w, i, j, c)
+    _, i, j, n = best
+    qa = pa + sum(np.sign(Ra[:, k] @ n) * ha[k] * Ra[:, k] for k in range(3) if k != i)
+    qb = pb - sum(np.sign(Rb[:, k] @ n) * hb[k] * Rb[:, k] for k in range(3) if k != j)
+    u, v, r = Ra[:, i], Rb[:, j], qb - qa
+    b = u @ v
+    s, t = (r @ u - b * (r @ v)) / (1 - b * b), (b * (r @ u) - r @ v) / (1 - b * b)
+    return 0.5 * (qa + s * u + qb + t * v)
+
+
+def box_incident_inside(m, g1, g2, pose):
+    """For a box pair decided by its smallest face overlap: (axis g1 -> g2, overlap, inside, over).  The
+    box owning that face is the reference, the other the incident one; `inside` says whether the
+    incident box's deepest corner along the axis (every corner within 1e-7 of the deepest)
+    projects into the reference face, 1e-5 clear of its rim.  Outside, the clip removes that
+    corner and the deepest contact is shallower than the overlap (an overhang)."""
+    (p1, R1), (p2, R2) = geom_frame(g1, pose), geom_frame(g2, pose)
+    h1, h2 = np.asarray(g1["size"], float), np.asarray(g2["size"], float)
+    face, ax, _, _, faces = box_sat(p1, R1, h1, p2, R2, h2)
+    k = int(np.argmin(faces))
+    (pr, Rr, hr), inc, s = ((p1, R1, h1), g2, ax) if k < 3 else ((p2, R2, h2), g1, -ax)
+    C = m.geom_points(inc, pose)
+    low = C[(C @ s) < (C @ s).min() + 1e-7]
+    loc = np.abs((low - pr) @ Rr)
+    over = max((np.delete(l, k % 3) - np.delete(hr, k % 3)).max() for l in loc)  # > 0: past the rim by this
+    return ax, face, bool(over < -1e-5), float(over)
+
+
+_HULL_EQ = {}
+
+
+def point_to_geom_distance(m, p, g, pose):
+    """Distance of a world point to the surface of a geom (unsigned; 0 on the surface).  Plane:
+    |z|.  Box and cylinder: closed form.  Hull: from qhull's facet equations, the depth below
+    the nearest facet inside, the height over the farthest-violated facet outside (the distance
+    itself where the nearest feature is a facet, a lower bound of it at an edge or a vertex)."""
+    p = np.asarray(p, float)
+    if g["type"] == "plane":
+        return abs(p[2])
+    if g["type"] == "mesh":
+        if g["mesh"] not in _HULL_EQ:
+            from scipy.spatial import ConvexHull
+
+            _HULL_EQ[g["mesh"]] = ConvexHull(m.hulls[g["mesh"]]).equations
+        bp, bR = pose[g["body"]]
+        eq = _HULL_EQ[g["mesh"]]
+        s = eq[:, :3] @ (bR.T @ (p - bp)) + eq[:, 3]
+        return float(abs(s.max()))
+    c, R = geom_frame(g, pose)
+    q = R.T @ (p - c)
+    if g["type"] == "box":
+        e = np.abs(q) - np.asarray(g["size"], float)
+    elif g["type"] == "cylinder":
+        e = np.array([np.hypot(q[0], q[1]) - g["size"][0], abs(q[2]) - g["size"][1]])
+    else:
+        raise ValueError(g["type"])
+    out = np.linalg.norm(np.maximum(e, 0.0))
+    return float(out if out > 0 else -e.max())
+
+
+# --------------------------------------------------------------------------- whole scenes, exactly
+def geom_group(g):
+    """The body group a collision geom belongs to (the sweep's classes are pairs of these)."""
+    if g["type"] == "plane":
+        return "floor"
+    if g["type"] == "mesh":
+        return "hull"
+    if g["type"] == "cylinder":
+        return "leg"
+    b = g["body"]
+    return "pad" if b.endswith("finger") else "table" if b == "table" else "bin" if b.startswith("bin") else "cube"
+
+
+class ExactScenes:
+    """Exact answers for every collision pair of the compiled model's pair list at a state: which
+    pairs penetrate, how deep, along which normal.  `ids` maps raw geom index -> compiled
+    collision-geom id (test_collision_kat.compiled_ids)."""
+
+    APART = 1e-3  # pairs certified farther apart than this are of no interest
+
+    def __init__(self, m, ids):
+        self.m, self.ids = m, ids
+        model = os.path.join(os.path.dirname(HERE), "mujoco_manip_amd", "model", "panda_pickplace.json")
+        back = {c: r for r, c in ids.items()}
+        cm = json.load(open(model))
+        col = {g: k for k, g in enumerate(cm["col_geoms"])}  # the pair list holds model geom ids
+        self.pairs = [tuple(sorted((back[col[a]], back[col[b]]), key=lambda r: (GT[m.geoms[r]["type"]], ids[r])))
+                      for a, b in cm["pairs"]]
+        # bounding spheres in the body frame, from the raw geometry
+        self.sphere = {}
+        for i, g in enumerate(m.geoms):
+            if g["type"] == "plane":
+                continue
+            if g["type"] == "mesh":
+                V = m.hulls[g["mesh"]]
+                c = 0.5 * (V.min(0) + V.max(0))
+                self.sphere[i] = (c, float(np.linalg.norm(V - c, axis=1).max()))
+            elif g["type"] == "box":
+                self.sphere[i] = (np.asarray(g["pos"], float), float(np.linalg.norm(g["size"])))
+            else:
+                self.sphere[i] = (np.asarray(g["pos"], float), float(np.hypot(*g["size"][:2])))
+
+    def order(self, ga, gb, n_ab):
+        """(g1, g2, normal g1 -> g2): the lower type first, equal types the lower compiled id."""
+        m, ids = self.m, self.ids
+        first = (GT[m.geoms[ga]["type"]], ids[ga]) < (GT[m.geoms[gb]["type"]], ids[gb])
+        return (ga, gb, np.asarray(n_ab, float)) if first else (gb, ga, -np.asarray(n_ab, float))
+
+    def pair(self, a, b, pose, nfacets=64):
+        """The exact answer of one ordered pair: dict(g1, g2, kind, depth, n [, facets])."""
+        m = self.m
+        ga, gb = m.geoms[a], m.geoms[b]
+        if ga["type"] == "plane":
+            d, n = plane_penetration(m, gb, pose)
+            return dict(g1=a, g2=b, kind="plane", depth=d, n=n)
+        kind = "box" if (ga["type"], gb["type"]) == ("box", "box") else "gjk"
+        d, n, fac = pair_penetration(m, ga, gb, pose, nfacets)
+        return dict(g1=a, g2=b, kind=kind, depth=d, n=n, facets=fac, exact=fac is not None)
+
+    def answers(self, q, nfacets=64):
+        """Every pair of the model's list not certified more than APART apart, at qpos q."""
+        m = self.m
+        pose = m.fk(q)
+        cen = {i: pose[m.geoms[i]["body"]][0] + pose[m.geoms[i]["body"]][1] @ c for i, (c, _) in self.sphere.items()}
+        out = []
+        for a, b in self.pairs:
+            ga, gb = m.geoms[a], m.geoms[b]
+            if ga["type"] == "plane":
+                if cen[b][2] - self.sphere[b][1] > self.APART:
+                    continue
+                ans = self.pair(a, b, pose)
+                if ans["depth"] > -self.APART:
+                    out.append(ans)
+                continue
+            dc = cen[b] - cen[a]
+            dist = np.linalg.norm(dc)
+            if dist - self.sphere[a][1] - self.sphere[b][1] > self.APART:
+                continue
+            # a cheap exact certificate: some direction along which the slabs are APART apart
+            trial = [dc / dist] if dist > 1e-9 else []
+            for g in (ga, gb):
+                if g["type"] != "mesh":
+                    R = pose[g["body"]][1]
+                    trial += [s * R[:, k] for k in range(3) for s in (-1, 1)]
+            if any(overlap(m, ga, gb, pose, n) < -self.APART for n in trial):
+                continue
+            ans = self.pair(a, b, pose, nfacets)
+            if ans["depth"] > -self.APART:
+                out.append(ans)
+        return out
