@@ -5,8 +5,8 @@
  * lengths, the env-step kernel's LDS layout, the dispatch order of env steps) and time the launches
  * for bench.py.  None of them changes a result: every choice here is bit-identical to the default
  * (tests/test_gpu.py: test_step_layouts_agree, test_step_order_bit_identical,
- * test_rollout_lanes_bit_identical, test_fused_rollout_bit_identical).  Same conventions as
- * mmx_api.h (0 or a negative MMX_E* code, never an abort). */
+ * test_rollout_lanes_bit_identical, test_fused_rollout_bit_identical; tests/test_step_budget.py).  Same
+ * conventions as mmx_api.h (0 or a negative MMX_E* code, never an abort). */
 #ifndef MMX_TUNING_H
 #define MMX_TUNING_H
 #include "mmx_api.h"
@@ -60,6 +60,26 @@ int mmx_rollout_render_overlap(const mmx_sim* sim);
  * envs' steps back to back inside each workgroup; the trajectories are bit-identical to one
  * launch per step.  0 for a null sim. */
 int mmx_rollout_steps_per_launch(const mmx_sim* sim);
+
+/* Time-budgeted launches of mmx_rollout_expert (1, the default; env MMX_ROLLOUT_BUDGET=0 sets 0 at create):
+ * on the 128-row layout without cameras, in calls whose lanes make at least 6 launches, a launch's
+ * workgroups stop at about the same time instead of after the same number of env steps, so the slots a
+ * launch frees are freed together and refilled by the lane's next launch.  The budget is the launch's
+ * length times the lane's measured time per env step (summed on the device by the lane's earlier launches:
+ * no host synchronisation); an env's step count stays within half a launch length of the fixed plan, the
+ * lane's first launch and the last launches of a call taper to fixed counts, and the call leaves every env
+ * at exactly n_env_steps.  So between the launches of one call envs may be at different step counts;
+ * nothing a caller can observe changes, and the results are bit-identical either way (envs are independent
+ * and plan, reset and step on the device).  mmx_step, the rollouts with per-step actions or a per-step
+ * record, camera rollouts and the 192-row layout always run fixed counts.
+ * MMX_EINVAL for other values; mmx_rollout_budget returns -1 for NULL.
+ * mmx_rollout_step_counts waits for the sim's stream and copies out (host int32 [num_envs]) the env steps
+ * each env made in the last budgeted call (zeros before one), and, when log is given, the counts after each
+ * launch of the env's lane (host int32 [log_launches][num_envs], zero rows past the lane's launches;
+ * log_launches must equal env MMX_ROLLOUT_LOG at create, which allocates the log: tests, diagnostics). */
+int mmx_set_rollout_budget(mmx_sim* sim, int32_t on);
+int mmx_rollout_budget(const mmx_sim* sim);
+int mmx_rollout_step_counts(mmx_sim* sim, int32_t* out, int32_t* log, int32_t log_launches);
 
 /* Per-launch kernel timing of mmx_rollout_expert (measurement): with enable = 1 every step-kernel
  * and render-kernel launch is bracketed by a HIP event pair on the stream it runs on (a new

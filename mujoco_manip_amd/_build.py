@@ -66,6 +66,9 @@ TEST_VARIANTS = {
     # displacement bound in the stats): results may not depend on which wave is late
     "libmmx_hdelay.so": ["MMX_HELPER_DELAY=1", "MMX_PROBE=14"],
     "libmmx_edelay.so": ["MMX_HELPER_DELAY=2", "MMX_PROBE=14"],
+    # the budgeted step launches' clock replaced by a cost of 1 + env % 3 "ticks" per env step (MMX_BUDGET_SYNTH in
+    # mmx_step.inc): envs progress unevenly in the same way on every machine (tests/test_step_budget.py)
+    "libmmx_synth.so": ["MMX_BUDGET_SYNTH=1"],
 }
 
 

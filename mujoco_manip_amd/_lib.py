@@ -155,6 +155,9 @@ _PROTOS = {
     "mmx_step_rows": (C.c_int, [_vp]),
     "mmx_set_step_order": (C.c_int, [_vp, _i32]),
     "mmx_step_order": (C.c_int, [_vp]),
+    "mmx_set_rollout_budget": (C.c_int, [_vp, _i32]),
+    "mmx_rollout_budget": (C.c_int, [_vp]),
+    "mmx_rollout_step_counts": (C.c_int, [_vp, _i32p, _i32p, _i32]),
     "mmx_rollout_launches": (C.c_int, [_vp, _i32]),
     "mmx_rollout_lanes": (C.c_int, [_vp]),
     "mmx_rollout_render_launches": (C.c_int, [_vp]),
@@ -164,6 +167,9 @@ _PROTOS = {
     "mmx_kernel_times": (C.c_int, [_vp, _fp, _i32p, _fp, _i32p]),
 }
 EXPORTED = tuple(_PROTOS)
+# exports that a library of an earlier revision lacks (tools/ab_build.py name@REV, loaded through MMX_LIB_PATH
+# as the other side of an A/B run); the product must have every one (__graft_entry__.build checks EXPORTED)
+_SINCE_BUDGET = ("mmx_set_rollout_budget", "mmx_rollout_budget", "mmx_rollout_step_counts")
 
 _lib = None
 
@@ -182,6 +188,8 @@ def load(build_if_missing: bool = True):
         _build.build(profile=profile)
     L = C.CDLL(path)
     for name, (restype, argtypes) in _PROTOS.items():
+        if name in _SINCE_BUDGET and os.environ.get("MMX_LIB_PATH") and not hasattr(L, name):
+            continue
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L
@@ -509,6 +517,27 @@ class Sim:
     @step_order.setter
     def step_order(self, on: bool):
         self._check(self.L.mmx_set_step_order(self.ptr, 1 if on else 0), "mmx_set_step_order")
+
+    @property
+    def rollout_budget(self) -> bool:
+        """rollout_expert's launches stop by the clock (True, the default where it applies: 128 rows, no
+        cameras, at least 6 launches per lane) or after fixed step counts; results are bit-identical either way."""
+        return bool(self.L.mmx_rollout_budget(self.ptr))
+
+    @rollout_budget.setter
+    def rollout_budget(self, on: bool):
+        self._check(self.L.mmx_set_rollout_budget(self.ptr, 1 if on else 0), "mmx_set_rollout_budget")
+
+    def rollout_step_counts(self, log_launches: int = 0):
+        """The env steps each env made in the last budgeted rollout_expert call (int32 [N]; waits for the sim's
+        stream), and with log_launches = MMX_ROLLOUT_LOG of the sim's creation also the counts after each
+        launch of the env's lane (int32 [log_launches, N])."""
+        out = np.zeros(self.num_envs, np.int32)
+        log = np.zeros((log_launches, self.num_envs), np.int32) if log_launches else None
+        self._check(self.L.mmx_rollout_step_counts(self.ptr, out.ctypes.data_as(_i32p),
+                                                   log.ctypes.data_as(_i32p) if log_launches else None, log_launches),
+                    "mmx_rollout_step_counts")
+        return (out, log) if log_launches else out
 
     @property
     def rollout_steps_per_launch(self) -> int:

@@ -48,6 +48,17 @@ struct mmx_sim {
   // env steps launched longest first (mmx_order_kernel; mmx_set_step_order, MMX_STEP_ORDER=0 at
   // create turns it off): the launch's order only, never its results
   int step_order = 1;
+  // time-budgeted launches of mmx_rollout_expert (128 rows, no cameras, lanes of at least 6 launches:
+  // rollout_bounds, mmx_plan.h; mmx_set_rollout_budget, MMX_ROLLOUT_BUDGET=0 at create turns it off): how an
+  // env's steps fall into launches only, never its results.  d_done [N] = the envs' step counts of the
+  // current call, d_acc [kMaxLanes][3][2] = each lane's steps and clock ticks per launch (MMXBudget),
+  // d_log [log_launches][N] = the counts after each launch of a lane (MMX_ROLLOUT_LOG=launches at create:
+  // tests, diagnostics)
+  int budget = 1;
+  int* d_done = nullptr;
+  unsigned long long* d_acc = nullptr;
+  int* d_log = nullptr;
+  int log_launches = 0;
   hipStream_t lane[kMaxLanes] = {};
   hipEvent_t ev_fork = nullptr, ev_join[kMaxLanes] = {};
   // camera rollouts render step k on their own stream beside step k + 1 (MMX_RENDER_OVERLAP=0 at
@@ -254,6 +265,10 @@ int mmx_create(const mmx_config* cfg, mmx_sim** out) {
   sim->d_mask = dalloc<unsigned char>(sim, n);
   sim->d_task = dalloc<int>(sim, n);
   sim->d_order = dalloc<int>(sim, n);
+  sim->d_done = dalloc<int>(sim, n);
+  sim->d_acc = dalloc<unsigned long long>(sim, 6 * kMaxLanes);
+  if (const char* v = std::getenv("MMX_ROLLOUT_LOG")) sim->log_launches = std::max(0, std::min(std::atoi(v), 1024));
+  if (sim->log_launches) sim->d_log = dalloc<int>(sim, n * sim->log_launches);
   if (cfg->image_size > 0) {  // camera renderer (mmx_render.hip): poses + RGB + segment ids
     const size_t px = static_cast<size_t>(cfg->image_size) * cfg->image_size;
     S.rpose = dalloc<float>(sim, 14 * 12 * n);
@@ -271,7 +286,9 @@ int mmx_create(const mmx_config* cfg, mmx_sim** out) {
   std::random_device rd;
   std::vector<unsigned long long> rng(4 * n);
   for (size_t i = 0; i < n; i++) pcg64_seed_row(&rng[4 * i], (static_cast<uint64_t>(rd()) << 32) ^ rd());
-  if (hipMemcpy(S.rng, rng.data(), rng.size() * sizeof(unsigned long long), hipMemcpyHostToDevice) != hipSuccess) {
+  if (hipMemcpy(S.rng, rng.data(), rng.size() * sizeof(unsigned long long), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(sim->d_done, 0, n * sizeof(int)) != hipSuccess ||
+      (sim->d_log && hipMemset(sim->d_log, 0, n * sim->log_launches * sizeof(int)) != hipSuccess)) {  // (no budgeted call yet: mmx_rollout_step_counts)
     mmx_destroy(sim);
     return MMX_EDEVICE;
   }
@@ -293,6 +310,7 @@ int mmx_create(const mmx_config* cfg, mmx_sim** out) {
   }
   sim->step_order = 1;
   if (const char* v = std::getenv("MMX_STEP_ORDER")) sim->step_order = std::atoi(v) != 0;
+  if (const char* v = std::getenv("MMX_ROLLOUT_BUDGET")) sim->budget = std::atoi(v) != 0;
   lanes = std::max(1, std::min(lanes, std::min(N, int(kMaxLanes))));
   if (hipEventCreateWithFlags(&sim->ev_fork, hipEventDisableTiming) != hipSuccess) lanes = 1;
   for (int l = 1; l < lanes; l++)
@@ -417,6 +435,22 @@ int mmx_set_step_order(mmx_sim* sim, int32_t on) {
   return MMX_OK;
 }
 int mmx_step_order(const mmx_sim* sim) { return sim ? sim->step_order : -1; }
+int mmx_set_rollout_budget(mmx_sim* sim, int32_t on) {
+  if (!sim || (on != 0 && on != 1)) return MMX_EINVAL;
+  sim->budget = on;
+  return MMX_OK;
+}
+int mmx_rollout_budget(const mmx_sim* sim) { return sim ? sim->budget : -1; }
+int mmx_rollout_step_counts(mmx_sim* sim, int32_t* out, int32_t* log, int32_t log_launches) {
+  if (!sim || (!out && !log) || (log && log_launches != sim->log_launches))
+    return sim ? fail(sim, MMX_EINVAL, "mmx_rollout_step_counts: bad arguments") : MMX_EINVAL;
+  DeviceGuard guard(sim);
+  const size_t n = static_cast<size_t>(sim->S.N);
+  hipError_t e = hipStreamSynchronize(sim->stream);
+  if (e == hipSuccess && out) e = hipMemcpy(out, sim->d_done, n * sizeof(int), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && log && log_launches) e = hipMemcpy(log, sim->d_log, n * log_launches * sizeof(int), hipMemcpyDeviceToHost);
+  return hip_check(sim, e, "mmx_rollout_step_counts");
+}
 
 int mmx_step(mmx_sim* sim, const float* action_dev, int32_t action_dim) {
   if (!sim || !action_dev) return MMX_EINVAL;
@@ -486,13 +520,16 @@ static RolloutPlan rollout_plan(const mmx_sim* sim, int n) {
 int mmx_rollout_launches(const mmx_sim* sim, int32_t n_env_steps) {
   return sim ? (int)rollout_plan(sim, n_env_steps).rounds : 0;
 }
-// The rollout's choreography, once, for both step kernels: `launch(S, base, count, nsteps, k0, st, order)`
+// The rollout's choreography, once, for both step kernels: `launch(S, base, count, nsteps, k0, st, order, B)`
 // launches `nsteps` env steps of envs [base, base + count) on `st`, k0 = the rollout step that lane has
 // reached (the trajectory kernel's action rows and record slices; the step kernel ignores it).  `what`
 // names the entry point in the error text.  (A template, not std::function: the launch is inlined.)
+// `budgeted` (mmx_rollout_expert on the 128-row kernel alone): when a lane makes enough launches
+// (rollout_bounds), every launch of the call gets B, its bounds on the envs' step counts and the lane's
+// step-time sums, in place of nsteps (null otherwise: the fixed count).
 extern "C++" {
 template <class Launch>
-static int rollout(mmx_sim* sim, int n, const char* what, Launch launch) {
+static int rollout(mmx_sim* sim, int n, const char* what, bool budgeted, Launch launch) {
   if (n <= 0) return MMX_OK;
   DeviceGuard guard(sim);
   const int N = sim->S.N;
@@ -509,7 +546,8 @@ static int rollout(mmx_sim* sim, int n, const char* what, Launch launch) {
       if (k >= 2) e = hipStreamWaitEvent(sim->stream, sim->ev_rend[k & 1], 0);
       int* ord = sim->step_order ? sim->d_order : nullptr;
       if (e == hipSuccess && ord) e = mmx_launch_order(&Sk, 0, N, ord, 1024, sim->stream);
-      if (e == hipSuccess) e = timed(sim, sim->stream, sim->t_step, [&] { return launch(&Sk, 0, N, 1, k, sim->stream, ord); });
+      if (e == hipSuccess)
+        e = timed(sim, sim->stream, sim->t_step, [&] { return launch(&Sk, 0, N, 1, k, sim->stream, ord, nullptr); });
       if (e == hipSuccess) e = hipEventRecord(sim->ev_step, sim->stream);
       if (e == hipSuccess) e = hipStreamWaitEvent(rs, sim->ev_step, 0);
       if (e == hipSuccess) e = timed(sim, rs, sim->t_render, [&] { return render(sim, Sk, 0, N, nullptr, rs); });
@@ -525,6 +563,21 @@ static int rollout(mmx_sim* sim, int n, const char* what, Launch launch) {
   // one step per launch.
   const RolloutPlan P = rollout_plan(sim, n);
   const int L = P.lanes;
+  // the launches' bounds; the counts and the lanes' sums start at zero before the fork (no host wait anywhere:
+  // a lane's launch reads the sums its earlier launches added, ordered by the lane's stream)
+  LaunchBounds bounds[kMaxLanes];
+  budgeted = budgeted && sim->budget && sim->S.image_size == 0;
+  bool use_budget = false;
+  for (int l = 0; l < L && budgeted; l++) {
+    bounds[l] = rollout_bounds(P.len[l], rollout_len(n, sim->fuse, false), true);
+    for (size_t r = 0; r < P.len[l].size(); r++) use_budget = use_budget || bounds[l].lo[r] < bounds[l].hi[r];
+  }
+  if (use_budget) {
+    e = hipMemsetAsync(sim->d_done, 0, sizeof(int) * N, sim->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(sim->d_acc, 0, sizeof(unsigned long long) * 6 * kMaxLanes, sim->stream);
+    if (e == hipSuccess && sim->d_log) e = hipMemsetAsync(sim->d_log, 0, sizeof(int) * N * sim->log_launches, sim->stream);
+    if (e != hipSuccess) return hip_check(sim, e, what);
+  }
   if (L > 1) {  // fork: every lane starts after the work already queued on the caller's stream
     e = hipEventRecord(sim->ev_fork, sim->stream);
     for (int l = 1; l < L && e == hipSuccess; l++) e = hipStreamWaitEvent(sim->lane[l], sim->ev_fork, 0);
@@ -541,7 +594,14 @@ static int rollout(mmx_sim* sim, int n, const char* what, Launch launch) {
       hipStream_t st = l ? sim->lane[l] : sim->stream;
       int* ord = sim->step_order ? sim->d_order + b0 : nullptr;  // the lane's slice of the order buffer
       if (ord) e = mmx_launch_order(&sim->S, b0, b1 - b0, ord, L > 1 ? 64 : 1024, st);
-      if (e == hipSuccess) e = timed(sim, st, sim->t_step, [&] { return launch(&sim->S, b0, b1 - b0, ns, k0[l], st, ord); });
+      MMXBudget B{sim->d_done, sim->d_acc + 6 * l, (int)r, nullptr, 0, 0, ns};
+      if (use_budget) {
+        B.lo = bounds[l].lo[r];
+        B.hi = bounds[l].hi[r];
+        if (sim->d_log && r < (size_t)sim->log_launches) B.log = sim->d_log + r * (size_t)N;
+      }
+      if (e == hipSuccess)
+        e = timed(sim, st, sim->t_step, [&] { return launch(&sim->S, b0, b1 - b0, ns, k0[l], st, ord, use_budget ? &B : nullptr); });
       k0[l] += ns;
     }
     if (e == hipSuccess && sim->S.image_size > 0)
@@ -561,9 +621,10 @@ static int rollout(mmx_sim* sim, int n, const char* what, Launch launch) {
 int mmx_rollout_expert(mmx_sim* sim, int32_t n_env_steps) {
   if (!sim || sim->S.action_mode != MMX_ACTION_ABS_POS) return MMX_EINVAL;
   const auto step = step_launchers(sim).step;
-  return rollout(sim, n_env_steps, "mmx_rollout_expert",
-                 [&](const MMXState* S, int base, int count, int ns, int, hipStream_t st, const int* ord) {
-                   return step(S, sim->expert_action, 4, 1, base, count, ns, st, ord);
+  return rollout(sim, n_env_steps, "mmx_rollout_expert", sim->step_rows == 128,
+                 [&](const MMXState* S, int base, int count, int ns, int, hipStream_t st, const int* ord, const MMXBudget* B) {
+                   return B ? mmx_launch_step_budget(S, B, sim->expert_action, 4, base, count, st, ord)
+                            : step(S, sim->expert_action, 4, 1, base, count, ns, st, ord);
                  });
 }
 
@@ -574,9 +635,10 @@ static int rollout_traj(mmx_sim* sim, const float* actions, int adim, int expert
   MMXTraj R{};
   if (rec) R = MMXTraj{rec->obs, rec->reward, rec->done, rec->reward_components, rec->target, rec->episode_i, rec->qpos, rec->qvel};
   const auto traj = step_launchers(sim).traj;
-  return rollout(sim, n, what, [&](const MMXState* S, int base, int count, int ns, int k0, hipStream_t st, const int* ord) {
-    return traj(S, &R, actions, adim, expert, base, count, ns, k0, st, ord);
-  });
+  return rollout(sim, n, what, false,
+                 [&](const MMXState* S, int base, int count, int ns, int k0, hipStream_t st, const int* ord, const MMXBudget*) {
+                   return traj(S, &R, actions, adim, expert, base, count, ns, k0, st, ord);
+                 });
 }
 
 int mmx_rollout_actions(mmx_sim* sim, const float* actions_dev, int32_t action_dim, int32_t n_env_steps,

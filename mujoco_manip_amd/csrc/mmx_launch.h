@@ -21,6 +21,9 @@ extern "C" {
 MMX_DECLARE_STEP_LAUNCHERS()
 MMX_DECLARE_STEP_LAUNCHERS(_l192)
 #undef MMX_DECLARE_STEP_LAUNCHERS
+// the 128-row build alone: expert steps up to cumulative bounds and a time budget (MMXBudget, mmx_state.h)
+hipError_t mmx_launch_step_budget(const MMXState* S, const MMXBudget* B, const float* action, int adim, int base, int count,
+                                  hipStream_t st, const int* order);
 
 // mmx_kernels.hip
 hipError_t mmx_launch_order(const MMXState* S, int base, int count, int* order, int threads, hipStream_t st);

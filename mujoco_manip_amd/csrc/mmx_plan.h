@@ -1,5 +1,6 @@
 // Launch plan of an n-step rollout.  Host code only, no HIP: tests/host/mmx_host_selftest.cpp prints the
-// plans under the sanitizers and tests/test_host_selftest.py checks them.
+// plans under the sanitizers and tests/test_host_selftest.py checks them; tests/host/mmx_plan_bounds_selftest.cpp
+// and tests/test_plan_bounds.py do the same for the bounds of the time-budgeted launches (rollout_bounds).
 //
 // Without cameras a launch runs `len` consecutive env steps of its lane's envs, len = min(fuse, ceil(n / 4));
 // lane l of L starts with a launch of l * len / L steps (none for lane 0), then launches of len, then the
@@ -82,6 +83,43 @@ inline RolloutPlan rollout_plan(int n, int lanes, int fuse, bool cameras, const 
     P.rounds = std::max(P.rounds, v.size());
   }
   return P;
+}
+
+// Time-budgeted launches (mmx_env_step_budget_kernel): the bounds on an env's step count of the call after each
+// launch of one lane, from the lane's lengths `len` (a row of rollout_plan), their sum n and the plan's
+// nominal length (rollout_len).  With c_j the count after launch j in the fixed plan and s_j a spread,
+//   lo_j = max(0, c_j - s_j),  hi_j = min(n, c_j + s_j):
+// a launch's workgroups stop by the clock anywhere in [lo_j, hi_j], so the lane's next launch finds slots
+// freed together, and no env is ever more than s_j steps off the plan.  s_j is nominal / 2 in the middle of
+// a call; 0 at the first launch (no step-time estimate yet) and at the last (every env ends at n); it halves
+// per launch towards the end (nominal / 2, / 4, / 8, 0), so the call's one full drain is a short one; and it
+// changes by at most len_j from one launch to the next, which keeps both sequences non-decreasing under any
+// MMX_PLAN.  Fixed (lo_j = hi_j = c_j) when `budget` is off or the lane makes fewer than 6 launches (the first,
+// one at the full spread, the three of the taper, the last): every call of fewer than 4 launches, and the
+// 20-step windows of the training driver (4 or 5 launches of 5 steps), whose measured plan stays as it is.
+struct LaunchBounds {
+  std::vector<int> lo, hi;
+};
+constexpr size_t kBudgetMinLaunches = 6;
+inline LaunchBounds rollout_bounds(const std::vector<int>& len, int nominal, bool budget) {
+  LaunchBounds B;
+  const size_t K = len.size();
+  std::vector<int> c(K), s(K, 0);
+  int n = 0;
+  for (size_t j = 0; j < K; j++) c[j] = n += len[j];
+  if (budget && K >= kBudgetMinLaunches) {
+    const int full = std::max(0, nominal / 2);
+    for (size_t j = 1; j + 1 < K; j++) {
+      const size_t d = K - 1 - j;  // launches after this one
+      s[j] = std::min(d >= 3 ? full : full >> (3 - d), s[j - 1] + len[j]);
+    }
+    for (size_t j = K - 1; j-- > 0;) s[j] = std::min(s[j], s[j + 1] + len[j + 1]);
+  }
+  for (size_t j = 0; j < K; j++) {
+    B.lo.push_back(std::max(0, c[j] - s[j]));
+    B.hi.push_back(std::min(n, c[j] + s[j]));
+  }
+  return B;
 }
 
 }  // namespace mmx_host

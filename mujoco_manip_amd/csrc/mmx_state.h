@@ -144,4 +144,20 @@ struct MMXTraj {
   float* qvel;               // [T][N][27]
 };
 
+// A time-budgeted step launch (mmx_env_step_budget_kernel; the plan: rollout_bounds of mmx_plan.h): the launch's
+// workgroups stop at about the same time instead of after the same number of env steps.  An env steps while its
+// count of the rollout call is below `hi`, and either below `lo` or the workgroup has run for less than
+// nominal * ticks / steps of the lane's previous launch (`acc`).  lo == hi is a fixed count.
+struct MMXBudget {
+  int* done;                // [N] env steps each env has made in the current rollout call
+  // [3][2] of the launch's lane: the env steps and their clock ticks summed over the workgroups of a launch.
+  // Launch r of the lane adds to pair r % 3, reads pair (r - 1) % 3 (complete: the lane's stream orders its
+  // launches) and clears pair (r + 1) % 3 for the next one.
+  unsigned long long* acc;
+  int round;                // r
+  int* log;                 // [N] `done` after this launch (diagnostics, tests), or null
+  int lo, hi;               // the bounds on `done` after this launch
+  int nominal;              // the launch's length in the fixed plan
+};
+
 #endif

@@ -3289,6 +3289,40 @@ enum { FSMP_PHASES = STAT_T_AUX3 - STAT_T_IK + 1, FSMP_STEP = FSMP_PHASES, FSMP_
 // (one copy per translation unit: mmx_kernels.hip reads out its own, the 128-row kernels', in
 // mmx_fsm_profile; the 192-row object's stays private to it)
 static __device__ double g_fsm_prof[11 * FSMP_N];
+// the profile's four stamps of an env step, for the step kernels' loops (below)
+#define FSMP_STEP_START const unsigned long long rt_step = wall_clock64() /* (the record load and the plan included) */
+#define FSMP_SUBSTEPS_START                                                         \
+  float snap[FSMP_N];                                                               \
+  const int fsm = EPI(EPI_FSM_STATE);                                               \
+  const unsigned long long t_step = clk_now();                                      \
+  if (LANE == 0) {                                                                  \
+    for (int j = 0; j < FSMP_PHASES; j++) snap[j] = g_E.stats[STAT_T_IK + j];       \
+    snap[FSMP_ITER] = g_E.stats[STAT_SOLVER_ITER];                                  \
+    snap[FSMP_NEFC] = g_E.stats[STAT_NEFC];                                         \
+    snap[FSMP_NCON] = g_E.stats[STAT_NCON];                                         \
+  }
+/* (read before step_finish stores the record: an autoreset does not clear stats) */
+#define FSMP_SUBSTEPS_END                                                                                           \
+  if (LANE == 0) {                                                                                                  \
+    double* g = g_fsm_prof + FSMP_N * min(max(fsm, 0), 10);                                                         \
+    for (int j = 0; j < FSMP_PHASES; j++) atomicAdd(g + j, (double)(g_E.stats[STAT_T_IK + j] - snap[j]));           \
+    atomicAdd(g + FSMP_ITER, (double)(g_E.stats[STAT_SOLVER_ITER] - snap[FSMP_ITER]));                              \
+    atomicAdd(g + FSMP_NEFC, (double)(g_E.stats[STAT_NEFC] - snap[FSMP_NEFC]));                                     \
+    atomicAdd(g + FSMP_NCON, (double)(g_E.stats[STAT_NCON] - snap[FSMP_NCON]));                                     \
+  }
+#define FSMP_STEP_END                                                                                               \
+  if (LANE == 0) {                                                                                                  \
+    double* g = g_fsm_prof + FSMP_N * min(max(fsm, 0), 10);                                                         \
+    atomicAdd(g + STAT_T_END - STAT_T_IK, (double)(g_E.stats[STAT_T_END] - snap[STAT_T_END - STAT_T_IK]));          \
+    atomicAdd(g + FSMP_STEP, (double)(clk_now() - t_step));                                                         \
+    atomicAdd(g + FSMP_RT, (double)(wall_clock64() - rt_step));                                                     \
+    atomicAdd(g + FSMP_COUNT, 1.0);                                                                                 \
+  }
+#else
+#define FSMP_STEP_START
+#define FSMP_SUBSTEPS_START
+#define FSMP_SUBSTEPS_END
+#define FSMP_STEP_END
 #endif
 
 // waves per SIMD the step kernel's register allocation is made for: 3 for the 128-row layout (168
@@ -3340,46 +3374,87 @@ MMX_NO_TAIL_MARK MMX_STEP_SYM(mmx_env_step_kernel)(MMXState S, const float* acti
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
       XSYNC();
     }
-#ifdef MMX_PHASE_CLOCK
-    const unsigned long long rt_step = wall_clock64();  // (the record load and the plan included)
-#endif
+    FSMP_STEP_START;
     step_begin(S, i, action, adim, expert);
     XSYNC();
-#ifdef MMX_PHASE_CLOCK
-    float snap[FSMP_N];
-    const int fsm = EPI(EPI_FSM_STATE);
-    const unsigned long long t_step = clk_now();
-    if (LANE == 0) {
-      for (int j = 0; j < FSMP_PHASES; j++) snap[j] = g_E.stats[STAT_T_IK + j];
-      snap[FSMP_ITER] = g_E.stats[STAT_SOLVER_ITER];
-      snap[FSMP_NEFC] = g_E.stats[STAT_NEFC];
-      snap[FSMP_NCON] = g_E.stats[STAT_NCON];
-    }
-#endif
+    FSMP_SUBSTEPS_START
     for (int sub = 0; sub < MMX_NSUBSTEP; sub++)
       substep(S.solver_max_iter, S.solver_tol, sub == MMX_NSUBSTEP - 1 ? contacts_dst(S, i) : nullptr);
-#ifdef MMX_PHASE_CLOCK
-    // (read before step_finish stores the record: an autoreset does not clear stats)
-    if (LANE == 0) {
-      double* g = g_fsm_prof + FSMP_N * min(max(fsm, 0), 10);
-      for (int j = 0; j < FSMP_PHASES; j++) atomicAdd(g + j, (double)(g_E.stats[STAT_T_IK + j] - snap[j]));
-      atomicAdd(g + FSMP_ITER, (double)(g_E.stats[STAT_SOLVER_ITER] - snap[FSMP_ITER]));
-      atomicAdd(g + FSMP_NEFC, (double)(g_E.stats[STAT_NEFC] - snap[FSMP_NEFC]));
-      atomicAdd(g + FSMP_NCON, (double)(g_E.stats[STAT_NCON] - snap[FSMP_NCON]));
-    }
-#endif
+    FSMP_SUBSTEPS_END
     step_finish(S, i);
-#ifdef MMX_PHASE_CLOCK
-    if (LANE == 0) {
-      double* g = g_fsm_prof + FSMP_N * min(max(fsm, 0), 10);
-      atomicAdd(g + STAT_T_END - STAT_T_IK, (double)(g_E.stats[STAT_T_END] - snap[STAT_T_END - STAT_T_IK]));
-      atomicAdd(g + FSMP_STEP, (double)(clk_now() - t_step));
-      atomicAdd(g + FSMP_RT, (double)(wall_clock64() - rt_step));
-      atomicAdd(g + FSMP_COUNT, 1.0);
-    }
-#endif
+    FSMP_STEP_END
   }
 }
+
+#if !MMX_STEP_HELPER
+// The launch's clock for the budget: the constant-rate counter (100 MHz) -- or, in the test build
+// libmmx_synth.so (MMX_BUDGET_SYNTH), a cost of 1 + env % 3 "ticks" per env step, k = the steps of this
+// launch so far: uneven progress that does not depend on the machine (tests/test_step_budget.py).
+DEV unsigned long long budget_now(int k, int i) {
+#ifdef MMX_BUDGET_SYNTH
+  return (unsigned long long)k * (unsigned long long)(1 + i % 3);
+#else
+  return wall_clock64();
+#endif
+}
+// mmx_env_step_kernel's expert step loop with a time budget in place of a step count (mmx_rollout_expert
+// on this, the one-wave layout, without cameras; MMXBudget in mmx_state.h).  The envs of a launch cost
+// 1.45 M to 2.5 M cycles a step by FSM phase, so after equal counts they end milliseconds apart and the
+// slots of the early ones stay empty until the lane's next launch; after equal times they end within a step
+// of each other, the cheap envs a few steps ahead of the plan and the dear ones behind it, every env
+// inside [lo, hi].  Each iteration is one single-step launch's body, as above, so the trajectories are
+// bit-identical however the steps fall into launches.  The test is made once per env step, after
+// step_finish, from scalar values (the count, the bounds, the clock), so it is the same for the whole wave;
+// lane 0 then writes the env's count back and adds the workgroup's steps and ticks to the launch's sums, from
+// which the lane's next launch (same stream: ordered after this one) takes its ticks per step.
+extern "C" __global__ void __launch_bounds__(MMX_STEP_THREADS) __attribute__((amdgpu_waves_per_eu(MMX_STEP_WAVES, MMX_STEP_WAVES)))
+MMX_NO_TAIL_MARK mmx_env_step_budget_kernel(MMXState S, MMXBudget B, const float* action, int adim, int base,
+                                            const int* order) {
+  const int i = order ? order[blockIdx.x] : base + blockIdx.x;
+  if (i >= S.N) return;
+  const int first = __builtin_amdgcn_readfirstlane(B.done[i]);
+  const unsigned long long t0 = budget_now(0, i);
+  unsigned long long budget = 0;
+  unsigned long long* const sum = B.acc + 2 * (B.round % 3);
+  if (blockIdx.x == 0 && LANE == 0) {  // the next launch's pair (MMXBudget: nobody reads or adds to it now)
+    unsigned long long* const next = B.acc + 2 * ((B.round + 1) % 3);
+    next[0] = next[1] = 0;
+  }
+  if (B.lo < B.hi) {
+    const unsigned long long* const last = B.acc + 2 * ((B.round + 2) % 3);
+    const unsigned long long steps = last[0], ticks = last[1];
+    if (steps) budget = (unsigned long long)((float)B.nominal * ((float)ticks / (float)steps));
+  }
+  // the step loop of mmx_env_step_kernel, its count open at the end: at least up to lo, then a step at a time
+  // while the clock and hi allow
+  const int most = B.hi - first;
+  int nsteps = max(B.lo - first, most > 0 && budget > 0 ? 1 : 0);
+  for (int k = 0; k < nsteps; k++) {
+    if (k) {  // the previous step's record stores complete before this step reloads it
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+      XSYNC();
+    }
+    FSMP_STEP_START;
+    step_begin(S, i, action, adim, 1);
+    XSYNC();
+    FSMP_SUBSTEPS_START
+    for (int sub = 0; sub < MMX_NSUBSTEP; sub++)
+      substep(S.solver_max_iter, S.solver_tol, sub == MMX_NSUBSTEP - 1 ? contacts_dst(S, i) : nullptr);
+    FSMP_SUBSTEPS_END
+    step_finish(S, i);
+    FSMP_STEP_END
+    if (k + 1 == nsteps) nsteps += __builtin_amdgcn_readfirstlane(nsteps < most && budget_now(nsteps, i) - t0 < budget);
+  }
+  if (LANE == 0) {
+    B.done[i] = first + nsteps;
+    if (B.log) B.log[i] = first + nsteps;
+    if (nsteps > 0) {
+      atomicAdd(sum, (unsigned long long)nsteps);
+      atomicAdd(sum + 1, budget_now(nsteps, i) - t0);
+    }
+  }
+}
+#endif
 
 // The env's outputs after an env step, into slice `row` = step * N + env of the trajectory arrays.
 // Runs on the env's wave right after step_finish and needs no barrier of its own: the observation,
@@ -3535,6 +3610,17 @@ extern "C" hipError_t MMX_STEP_SYM(mmx_launch_step)(const MMXState* S, const flo
                      nsteps, order);
   return hipGetLastError();
 }
+#if !MMX_STEP_HELPER
+// expert steps of envs [base, base+count) up to the bounds and the budget of B (the one-wave layout only)
+extern "C" hipError_t mmx_launch_step_budget(const MMXState* S, const MMXBudget* B, const float* action, int adim, int base,
+                                             int count, hipStream_t st, const int* order) {
+  if (count <= 0) return hipSuccess;
+  if (!B->done || !B->acc || B->round < 0 || B->lo < 0 || B->lo > B->hi) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(mmx_env_step_budget_kernel, dim3(count), dim3(MMX_STEP_THREADS), step_lds_pad(), st, *S, *B, action, adim,
+                     base, order);
+  return hipGetLastError();
+}
+#endif
 // n substeps of every env, one launch each (mmx_physics_step)
 extern "C" hipError_t MMX_STEP_SYM(mmx_launch_physics)(const MMXState* S, int n, int with_ik, hipStream_t st) {
   for (int sub = 0; sub < n; sub++) {

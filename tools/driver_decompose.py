@@ -13,6 +13,11 @@ The rate of a window is env_steps / T = fill / (busy / env_steps): the window's 
 (drain / launch overhead) times the inverse of its mean cycles per env step (phase mix).  Against
 the stationary window: rate_W / rate_S = (fill_W / fill_S) x (cyc_S / cyc_W); the first factor is
 the per-call overhead, the second the phase mix.  Writes gpurun_out/driver_decompose.json."""
+# Options: --budget 0|1 sets the time-budgeted launches of the long window (Sim.rollout_budget; the 20-step
+# windows run fixed counts either way), so both sides of that A/B run from this script; a library of an earlier
+# revision (MMX_LIB_PATH) has no such switch and takes no --budget.  --out NAME gives the result file that name,
+# in the same directory.
+import argparse
 import ctypes as C
 import json
 import os
@@ -31,7 +36,7 @@ FSM = ["idle", "pre_grasp", "grasp", "close_gripper", "lift", "move_to_bin", "se
        "retreat", "done"]
 
 
-def main(N=4096, warm=5, steps=20, windows=5, long_steps=512):
+def main(N=4096, warm=5, steps=20, windows=5, long_steps=512, budget=None, out_name=None):
     assert os.environ.get("MMX_PROFILE", "0") not in ("", "0"), "needs the profile build (MMX_PROFILE=1)"
     L = _lib.load()
     nf = L.mmx_fsm_profile_fields()
@@ -41,6 +46,8 @@ def main(N=4096, warm=5, steps=20, windows=5, long_steps=512):
     SLOTS = torch.cuda.get_device_properties(0).multi_processor_count * 12  # twelve envs per CU (128-row build)
     env = PickPlaceVecEnv(N, tasks="all", action_mode="abs_pos", reward_type="staged", randomize_objects=True,
                           autoreset=True, image_size=0)
+    if budget is not None:
+        env.sim.rollout_budget = bool(budget)
     env.reset(seed=[_lib.episode_seed(42, i) for i in range(N)])
     env.rollout_expert(warm)
     torch.cuda.synchronize()
@@ -66,7 +73,8 @@ def main(N=4096, warm=5, steps=20, windows=5, long_steps=512):
                 "phase_cycles_per_env_step": {FSM[s]: float(cyc[s] / cnt[s]) for s in range(11) if cnt[s]}}
 
     out = {"config": {"envs": N, "warmup": warm, "steps": steps, "windows": windows, "long_steps": long_steps,
-                      "lanes": env.sim.rollout_lanes, "launches_per_lane": env.sim.rollout_launches(steps)},
+                      "lanes": env.sim.rollout_lanes, "launches_per_lane": env.sim.rollout_launches(steps),
+                      "rollout_budget": budget, "lib": os.environ.get("MMX_LIB_PATH", "")},
            "windows": [window(steps) for _ in range(windows)]}
     env.rollout_expert(64)  # into the stationary mix (episodes desynchronised by autoresets)
     out["stationary"] = window(long_steps)
@@ -86,10 +94,16 @@ def main(N=4096, warm=5, steps=20, windows=5, long_steps=512):
     os.makedirs(os.path.join(REPO, "gpurun_out"), exist_ok=True)
     with open(os.path.join(REPO, "gpurun_out", "driver_decompose.json"), "w") as f:
         json.dump(out, f, indent=1)
+    if out_name:
+        os.replace(f.name, os.path.join(os.path.dirname(f.name), out_name))
     print(json.dumps(out["summary"]))
     for w in ws:
         print(round(w["rate"]), round(w["overhead_factor"], 3), round(w["phase_mix_factor"], 3))
 
 
 if __name__ == "__main__":
-    main()
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--budget", type=int, choices=(0, 1), default=None)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    main(budget=a.budget, out_name=a.out)

@@ -9,7 +9,8 @@ import collections
 import re
 import sys
 
-FUNCS = ("_Z7substepifPf", "mmx_env_step_kernel", "mmx_env_step_kernel_l192", "_Z10step_beginRK8MMXStateiPKfii",
+FUNCS = ("_Z7substepifPf", "mmx_env_step_kernel", "mmx_env_step_budget_kernel", "mmx_env_step_kernel_l192",
+         "_Z10step_beginRK8MMXStateiPKfii",
          "_Z11step_finishRK8MMXStatei")  # (a listing holds one of the two kernels: the other is left out)
 
 # a function's label: `name:` in a -S listing, `0000000000001900 <name>:` in llvm-objdump -d output
@@ -44,7 +45,7 @@ def frames(path):
     for f in FUNCS:
         seg = re.search(rf"\.set (?:\.L)?{re.escape(f)}\.private_seg_size, (\d+)(\+max)?", txt)
         vg = re.search(rf"\.set (?:\.L)?{re.escape(f)}\.num_vgpr, (?:max\()?(\d+)", txt)
-        if f.startswith("mmx_env_step_kernel") and not seg:
+        if f.startswith("mmx_env_step_") and not seg:
             continue
         out[f] = {"private_seg_bytes_per_lane": int(seg.group(1)) if seg else None,
                   "plus_callees": bool(seg and seg.group(2)), "vgpr": int(vg.group(1)) if vg else None, **ops[f]}

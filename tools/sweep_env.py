@@ -2,6 +2,8 @@
 on one bench configuration: every setting runs once per round, rounds interleaved, and the report
 gives each setting's median line value and its windows.  Run on the GPU box from the repo root:
     python tools/sweep_env.py --bench-args "--steps 20 --warmup 5" --rounds 2 "" "MMX_PLAN=1,1" ...
+Other settings: "MMX_ROLLOUT_BUDGET=0" = fixed-count launches; "MMX_LIB_PATH=build/libmmx_x.so" = a library of
+tools/ab_build.py as one side.
 ("" = the library's defaults).  Writes gpurun_out/sweep_env.json.  Experiment infrastructure."""
 import argparse
 import json
