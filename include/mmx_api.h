@@ -223,6 +223,84 @@ int mmx_snapshot(mmx_sim* sim, void* snap_dev, int64_t rec_bytes);
 int mmx_restore(mmx_sim* sim, const void* snap_dev, int64_t rec_bytes, int32_t n_records,
                 const int32_t* src_dev);
 
+/* MPPI planning on the device: sample, branch, roll out, reweight (no reference counterpart: the sampling
+ * planner that mmx_snapshot / mmx_restore were added for, as one library call with no host round trip).
+ * Information-theoretic model-predictive path integral control; random shooting is its temperature-0 limit.
+ * One camera-less planner sim of N = M * K envs serves M controlled envs with K candidates each: planner
+ * env i = m * K + k rolls out candidate k of controlled env m.  A is the planner sim's action dimension
+ * (4, 8 or 10).
+ * mmx_mppi_plan, asynchronous on the planner sim's stream, with no host synchronisation and no device
+ * allocation after mmx_mppi_create:
+ *  1. sample: xi is the caller's xi_dev or the library's draw, Philox4x32-10 with key = seed and counter =
+ *     (call low, call high, i, 4 t + a / 4), whose four outputs give two Box-Muller pairs: component a takes
+ *     normal a % 4 of its block, so element (t, i, a) depends on seed, call, t, i and a only, never on K, M or
+ *     the launch shape.  eps_0 = xi_0, eps_t = beta eps_{t-1} + sqrt(1 - beta^2) xi_t; candidate k = 0 of
+ *     every group gets eps = 0 (the nominal plan is always a candidate, whatever xi_dev holds); then
+ *     actions[t][i][a] = clamp(nominal[t][m][a] + sigma[a] eps[t][i][a], low[a], high[a]);
+ *  2. branch: planner env i takes record i / K of the n_records = M records at snap_dev (the restore kernel
+ *     of mmx_restore with a src array built at create).  rec_bytes may be MMX_SNAPSHOT_BYTES or
+ *     MMX_SNAPSHOT_BYTES_CAMERAS: the planner reads the fixed MMX_SNAPSHOT_BYTES prefix of each record at
+ *     stride rec_bytes, so a controlled sim with cameras can be planned for (mmx_restore itself keeps
+ *     rejecting a size mismatch);
+ *  3. roll out: actions through the machinery of mmx_rollout_actions, reward and done recorded;
+ *  4. reweight: R_i = sum_t gamma^t reward[t][i] alive_t with alive_0 = 1, alive_{t+1} = alive_t and not
+ *     (terminated_t or truncated_t): the ending step's reward counts, nothing after it.  A candidate whose
+ *     return is not finite (a test of the bits) is excluded: weight 0.  Per group: best = the argmax of R
+ *     (lowest k on ties), w_k = exp((R_k - max R) / lambda) normalised to sum 1, or one-hot on best when
+ *     temperature == 0; nominal'[t][m] = sum_k w_k actions[t][i] (kept within [low, high]);
+ *     action_out[m] = nominal'[0][m]; then the shift nominal[t] = nominal'[t + 1] for t < H - 1, the last
+ *     step repeated.  A group whose candidates are all excluded keeps its nominal as it was (no shift), gets
+ *     weights 0 and best -1, and action_out[m] = nominal[0][m].  Every sum has a fixed order and no
+ *     floating-point atomics: the same inputs give the same bits on every run.
+ * MMX_EINVAL, with nothing launched, for a NULL planner, blob or output, a blob that is not 16-byte aligned,
+ * rec_bytes other than the two record sizes, and n_records != M.  mmx_mppi_create returns MMX_EINVAL for a
+ * config field outside its stated range, low[a] > high[a], sigma[a] < 0 or a value of these that is not
+ * finite (a < A; an unbounded component takes +-FLT_MAX), a planner sim with cameras (rendering candidates
+ * is waste) and num_envs % samples != 0.  mmx_mppi_reset sets every step of
+ * every nominal plan to action_dev [M][A] (kept within [low, high]) and the call counter to 0; the counter
+ * increments by one per successful mmx_mppi_plan call, with caller-supplied xi_dev too.  The planner never
+ * touches the controlled sim: the caller snapshots it, and orders that snapshot before the plan call when
+ * the two sims use different streams; snap_dev, xi_dev and action_out_dev must stay valid until the planner
+ * sim's stream has run the call.  Equal configuration of the two sims is the caller's responsibility,
+ * as for mmx_restore.  mmx_mppi_destroy before mmx_destroy of the planner sim; the buffers of
+ * mmx_mppi_get_buffers are valid until then. */
+#define MMX_MPPI_MAX_HORIZON 64
+#define MMX_MPPI_MAX_ADIM 10
+typedef struct mmx_mppi mmx_mppi;
+typedef struct {
+  int32_t horizon;      /* H env steps per candidate, 1 .. MMX_MPPI_MAX_HORIZON */
+  int32_t samples;      /* K >= 2 candidates per controlled env; planner num_envs % K == 0, M = num_envs / K */
+  float temperature;    /* lambda > 0 (with a finite 1 / lambda): w_k ~ exp((R_k - max R) / lambda); 0: all
+                           weight on the best candidate, lowest k on ties */
+  float discount;       /* gamma in (0, 1] */
+  float noise_beta;     /* in [0, 1): eps_0 = xi_0, eps_t = beta eps_{t-1} + sqrt(1 - beta^2) xi_t */
+  float sigma[MMX_MPPI_MAX_ADIM], low[MMX_MPPI_MAX_ADIM], high[MMX_MPPI_MAX_ADIM];  /* per action component;
+                           the first A are read */
+  uint64_t seed;
+} mmx_mppi_config;
+typedef struct {        /* planner-owned device arrays, valid until mmx_mppi_destroy; i = m * K + k */
+  float* nominal;       /* [H][M][A] */
+  float* noise;         /* [H][M*K][A] eps of the last call (0 for k == 0) */
+  float* actions;       /* [H][M*K][A] the candidates the last call rolled out */
+  float* reward;        /* [H][M*K] */
+  int32_t* done;        /* [H][M*K][3] */
+  float* returns;       /* [M*K] */
+  float* weights;       /* [M*K], each group of K sums to 1 */
+  int32_t* best;        /* [M] argmax_k R within the group */
+} mmx_mppi_buffers;
+int  mmx_mppi_create(mmx_sim* planner, const mmx_mppi_config* cfg, mmx_mppi** out);
+void mmx_mppi_destroy(mmx_mppi* p);
+int  mmx_mppi_reset(mmx_mppi* p, const float* action_dev /* [M][A]: every step of every nominal plan */);
+int  mmx_mppi_plan(mmx_mppi* p, const void* snap_dev, int64_t rec_bytes, int32_t n_records,
+                   const float* xi_dev /* NULL, or [H][M*K][A] standard-normal draws */,
+                   float* action_out_dev /* [M][A] */);
+int  mmx_mppi_get_buffers(mmx_mppi* p, mmx_mppi_buffers* out);
+/* Reweight-layer harness: step 4 of mmx_mppi_plan alone, on the planner's reward, done, actions and nominal
+ * arrays as they stand (a test writes its own rewards and done flags there): returns, weights, best, the
+ * shifted nominal and action_out as after a plan call.  No sampling, branch or rollout, and the call counter
+ * stays.  Asynchronous on the planner sim's stream; MMX_EINVAL for a NULL planner or output. */
+int  mmx_mppi_reweight(mmx_mppi* p, float* action_out_dev);
+
 /* Batched PNG encoder (dataset emission, generate_dataset.py:250-260: LeRobot embeds image
  * features as PNG files).  Encodes n RGB8 images (device, image i at rgb_dev + i * img_stride,
  * rows of 3 * width bytes, height <= 1024, width <= MMX_PNG_MAX_WIDTH: the encoder's row-above match

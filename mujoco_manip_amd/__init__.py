@@ -7,7 +7,7 @@ environments in lockstep by HIP kernels (libmmx.so, C-ABI in include/mmx_api.h).
 """
 from .constants import ACTION_REPEAT, ALL_TASKS, BINS, OBJECTS, TASK_SETS  # noqa: F401
 
-__all__ = ["PickPlaceVecEnv", "PickPlaceGymEnv", "Snapshot", "build_library", "episode_seed"]
+__all__ = ["PickPlaceVecEnv", "PickPlaceGymEnv", "Snapshot", "MppiPlanner", "build_library", "episode_seed"]
 
 
 def build_library(force: bool = False) -> str:
@@ -31,6 +31,10 @@ def __getattr__(name):
         from .vec_env import Snapshot
 
         return Snapshot
+    if name == "MppiPlanner":
+        from .planner import MppiPlanner
+
+        return MppiPlanner
     if name == "PickPlaceGymEnv":
         from .gym_env import PickPlaceGymEnv
 

@@ -79,6 +79,26 @@ class MMXTrajectory(C.Structure):
     ]
 
 
+MPPI_MAX_HORIZON, MPPI_MAX_ADIM = 64, 10  # include/mmx_api.h MMX_MPPI_MAX_HORIZON, MMX_MPPI_MAX_ADIM
+
+
+class MMXMppiConfig(C.Structure):
+    """mmx_mppi_config (include/mmx_api.h)."""
+    _fields_ = [
+        ("horizon", C.c_int32), ("samples", C.c_int32), ("temperature", C.c_float), ("discount", C.c_float),
+        ("noise_beta", C.c_float), ("sigma", C.c_float * MPPI_MAX_ADIM), ("low", C.c_float * MPPI_MAX_ADIM),
+        ("high", C.c_float * MPPI_MAX_ADIM), ("seed", C.c_uint64),
+    ]
+
+
+class MMXMppiBuffers(C.Structure):
+    """mmx_mppi_buffers (include/mmx_api.h): planner-owned device arrays."""
+    _fields_ = [
+        ("nominal", C.c_void_p), ("noise", C.c_void_p), ("actions", C.c_void_p), ("reward", C.c_void_p),
+        ("done", C.c_void_p), ("returns", C.c_void_p), ("weights", C.c_void_p), ("best", C.c_void_p),
+    ]
+
+
 # per-env width and dtype of every trajectory array
 TRAJ_FIELDS = {"obs": (NOBS, "float32"), "reward": (1, "float32"), "done": (3, "int32"),
                "reward_components": (6, "float32"), "target": (4, "float32"), "episode_i": (EPI_N, "int32"),
@@ -132,6 +152,12 @@ _PROTOS = {
     "mmx_snapshot_bytes": (_i64, [_vp]),
     "mmx_snapshot": (C.c_int, [_vp, _vp, _i64]),
     "mmx_restore": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
+    "mmx_mppi_create": (C.c_int, [_vp, C.POINTER(MMXMppiConfig), C.POINTER(_vp)]),
+    "mmx_mppi_destroy": (None, [_vp]),
+    "mmx_mppi_reset": (C.c_int, [_vp, _vp]),
+    "mmx_mppi_plan": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp]),
+    "mmx_mppi_get_buffers": (C.c_int, [_vp, C.POINTER(MMXMppiBuffers)]),
+    "mmx_mppi_reweight": (C.c_int, [_vp, _vp]),
     "mmx_png_bound": (_i64, [_i32, _i32]),
     "mmx_png_scratch": (_i64, [_i32, _i32]),
     "mmx_png_encode": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
@@ -170,6 +196,8 @@ EXPORTED = tuple(_PROTOS)
 # exports that a library of an earlier revision lacks (tools/ab_build.py name@REV, loaded through MMX_LIB_PATH
 # as the other side of an A/B run); the product must have every one (__graft_entry__.build checks EXPORTED)
 _SINCE_BUDGET = ("mmx_set_rollout_budget", "mmx_rollout_budget", "mmx_rollout_step_counts")
+_SINCE_MPPI = ("mmx_mppi_create", "mmx_mppi_destroy", "mmx_mppi_reset", "mmx_mppi_plan", "mmx_mppi_get_buffers",
+               "mmx_mppi_reweight")
 
 _lib = None
 
@@ -188,7 +216,7 @@ def load(build_if_missing: bool = True):
         _build.build(profile=profile)
     L = C.CDLL(path)
     for name, (restype, argtypes) in _PROTOS.items():
-        if name in _SINCE_BUDGET and os.environ.get("MMX_LIB_PATH") and not hasattr(L, name):
+        if name in _SINCE_BUDGET + _SINCE_MPPI and os.environ.get("MMX_LIB_PATH") and not hasattr(L, name):
             continue
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
@@ -596,3 +624,66 @@ class Sim:
         ptr = getattr(self.buffers, name)
         shape = (self.num_envs, nfield) if nfield > 1 else (self.num_envs,)
         return torch.as_tensor(_DevArray(ptr, shape, dtype, self), device=f"cuda:{self.cfg.device}")
+
+
+class Mppi:
+    """Owner of one mmx_mppi bound to a camera-less planner Sim of M * samples envs (mmx_mppi_* of
+    include/mmx_api.h).  Close it before the planner sim."""
+
+    def __init__(self, sim: Sim, *, horizon: int, samples: int, sigma, low, high, temperature: float = 1.0,
+                 discount: float = 1.0, noise_beta: float = 0.0, seed: int = 0):
+        A = sim.action_dim
+        for name, v in (("sigma", sigma), ("low", low), ("high", high)):
+            if len(v) != A:
+                raise ValueError(f"{name} must have {A} entries (the action dimension), got {len(v)}")
+        cfg = MMXMppiConfig(horizon=int(horizon), samples=int(samples), temperature=float(temperature),
+                            discount=float(discount), noise_beta=float(noise_beta), seed=int(seed) & (2**64 - 1))
+        for a in range(A):
+            cfg.sigma[a], cfg.low[a], cfg.high[a] = float(sigma[a]), float(low[a]), float(high[a])
+        self.sim, self.cfg, self.L = sim, cfg, sim.L
+        self.H, self.K, self.A = int(horizon), int(samples), A
+        ptr = C.c_void_p()
+        rc = self.L.mmx_mppi_create(sim.ptr, C.byref(cfg), C.byref(ptr))
+        if rc != 0 or not ptr.value:
+            raise ValueError(f"mmx_mppi_create failed ({rc}): {self.L.mmx_last_error(sim.ptr).decode()}")
+        self.ptr = ptr
+        self.M = sim.num_envs // self.K
+        self.buffers = MMXMppiBuffers()
+        sim._check(self.L.mmx_mppi_get_buffers(self.ptr, C.byref(self.buffers)), "mmx_mppi_get_buffers")
+
+    def close(self):
+        if getattr(self, "ptr", None) is not None and self.ptr.value:
+            self.L.mmx_mppi_destroy(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, action_ptr: int):
+        """Every step of every nominal plan = the device action [M][A]; the call counter to 0 (mmx_mppi_reset)."""
+        self.sim._check(self.L.mmx_mppi_reset(self.ptr, C.c_void_p(action_ptr)), "mmx_mppi_reset")
+
+    def plan(self, snap_ptr: int, rec_bytes: int, n_records: int, xi_ptr: int | None, out_ptr: int):
+        """One control step for the M records at snap_ptr -> the device action [M][A] at out_ptr (mmx_mppi_plan;
+        asynchronous on the planner sim's stream)."""
+        self.sim._check(self.L.mmx_mppi_plan(self.ptr, C.c_void_p(snap_ptr), int(rec_bytes), int(n_records),
+                                             C.c_void_p(xi_ptr) if xi_ptr else None, C.c_void_p(out_ptr)), "mmx_mppi_plan")
+
+    def reweight(self, out_ptr: int):
+        """The reweight pass alone on the planner's arrays as they stand (mmx_mppi_reweight: a test harness)."""
+        self.sim._check(self.L.mmx_mppi_reweight(self.ptr, C.c_void_p(out_ptr)), "mmx_mppi_reweight")
+
+    def views(self) -> dict:
+        """Zero-copy torch views of the planner-owned arrays (mmx_mppi_buffers)."""
+        import torch
+
+        H, M, K, A, N = self.H, self.M, self.K, self.A, self.M * self.K
+        shapes = {"nominal": ((H, M, A), "<f4"), "noise": ((H, N, A), "<f4"), "actions": ((H, N, A), "<f4"),
+                  "reward": ((H, N), "<f4"), "done": ((H, N, 3), "<i4"), "returns": ((N,), "<f4"),
+                  "weights": ((N,), "<f4"), "best": ((M,), "<i4")}
+        dev = f"cuda:{self.sim.cfg.device}"
+        return {n: torch.as_tensor(_DevArray(getattr(self.buffers, n), shp, t, self), device=dev)
+                for n, (shp, t) in shapes.items()}

@@ -4,9 +4,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <new>
 #include <random>
 #include <string>
 #include <vector>
@@ -14,6 +17,7 @@
 #include "../../include/mmx_api.h"
 #include "../../include/mmx_tuning.h"
 #include "mmx_launch.h"
+#include "mmx_mppi.h"
 #include "mmx_plan.h"
 #include "mmx_seed.h"
 #include "mmx_state.h"
@@ -85,6 +89,19 @@ struct mmx_sim {
   int* q_task = nullptr;
   unsigned long long* q_rng = nullptr;
   int q_n = -1;
+};
+
+// A planner bound to its (camera-less) planner sim: the launch parameters, its device arrays (its own
+// allocations, freed by mmx_mppi_destroy), the branch's src array (i -> i / K) and the call counter
+struct mmx_mppi {
+  mmx_sim* sim = nullptr;
+  int device = 0;  // the sim's (kept for mmx_mppi_destroy)
+  MppiParams P{};
+  MppiBufs B{};
+  float* box = nullptr;  // [3][MMX_MPPI_MAX_ADIM] sigma, low, high
+  int* src = nullptr;    // [N]
+  uint64_t call = 0;
+  std::vector<void*> allocs;
 };
 
 namespace {
@@ -843,6 +860,127 @@ int mmx_restore(mmx_sim* sim, const void* snap_dev, int64_t rec_bytes, int32_t n
   // the restored envs' images and segment ids, redrawn from the restored poses with the sim's current effects
   if (e == hipSuccess && mask) e = render(sim, S, 0, S.N, mask, sim->stream);
   return hip_check(sim, e, "mmx_restore");
+}
+
+// MPPI planner (mmx_mppi.hip, mmx_mppi.h): sample -> branch (the restore kernel at the blob's stride) -> the
+// trajectory rollout with reward and done recorded -> reweight, all queued on the planner sim's stream.
+int mmx_mppi_create(mmx_sim* sim, const mmx_mppi_config* c, mmx_mppi** out) {
+  if (out) *out = nullptr;
+  if (!sim || !c || !out) return sim ? fail(sim, MMX_EINVAL, "mmx_mppi_create: NULL argument") : MMX_EINVAL;
+  if (sim->S.image_size > 0) return fail(sim, MMX_EINVAL, "mmx_mppi_create: the planner sim must have no cameras");
+  const int A = kDim[sim->S.action_mode], N = sim->S.N;
+  // (written so that a NaN fails every range test)
+  bool ok = c->horizon >= 1 && c->horizon <= MMX_MPPI_MAX_HORIZON && c->samples >= 2 && N % c->samples == 0;
+  // (a temperature whose reciprocal overflows would turn the best candidate's exponent 0 * Inf into NaN)
+  ok = ok && c->temperature >= 0.f && c->temperature <= FLT_MAX && (c->temperature == 0.f || 1.f / c->temperature <= FLT_MAX);
+  ok = ok && c->discount > 0.f && c->discount <= 1.f;
+  ok = ok && c->noise_beta >= 0.f && c->noise_beta < 1.f && A <= MMX_MPPI_MAX_ADIM;
+  for (int a = 0; a < A && ok; a++)
+    ok = c->sigma[a] >= 0.f && c->sigma[a] <= FLT_MAX && c->low[a] <= c->high[a] && c->low[a] >= -FLT_MAX && c->high[a] <= FLT_MAX;
+  if (!ok) return fail(sim, MMX_EINVAL, "mmx_mppi_create: a config field is outside its range, or num_envs % samples != 0");
+  DeviceGuard guard(sim);
+  mmx_mppi* p = new (std::nothrow) mmx_mppi();
+  if (!p) return fail(sim, MMX_ENOMEM, "mmx_mppi_create: host allocation");
+  p->sim = sim;
+  p->device = sim->cfg.device;
+  MppiParams& P = p->P;
+  P.H = c->horizon, P.K = c->samples, P.M = N / c->samples, P.A = A;
+  P.inv_lambda = c->temperature > 0.f ? 1.f / c->temperature : 0.f;
+  P.gamma = c->discount;
+  P.beta = c->noise_beta;
+  P.beta_c = std::sqrt(1.f - c->noise_beta * c->noise_beta);
+  P.seed_lo = (uint32_t)c->seed, P.seed_hi = (uint32_t)(c->seed >> 32);
+  const size_t H = (size_t)P.H, M = (size_t)P.M, n = (size_t)N, a = (size_t)A;
+  auto alloc = [&](size_t bytes) -> void* {
+    void* d = nullptr;
+    if (hipMalloc(&d, bytes) != hipSuccess) return nullptr;
+    if (hipMemset(d, 0, bytes) != hipSuccess) {
+      (void)hipFree(d);
+      return nullptr;
+    }
+    p->allocs.push_back(d);
+    return d;
+  };
+  MppiBufs& B = p->B;
+  B.nominal = static_cast<float*>(alloc(H * M * a * 4));
+  B.noise = static_cast<float*>(alloc(H * n * a * 4));
+  B.actions = static_cast<float*>(alloc(H * n * a * 4));
+  B.reward = static_cast<float*>(alloc(H * n * 4));
+  B.done = static_cast<int*>(alloc(H * n * 3 * 4));
+  B.returns = static_cast<float*>(alloc(n * 4));
+  B.weights = static_cast<float*>(alloc(n * 4));
+  B.best = static_cast<int*>(alloc(M * 4));
+  p->box = static_cast<float*>(alloc(3 * MMX_MPPI_MAX_ADIM * 4));
+  p->src = static_cast<int*>(alloc(n * 4));
+  if (p->allocs.size() != 10) {
+    mmx_mppi_destroy(p);
+    return fail(sim, MMX_ENOMEM, "mmx_mppi_create: device allocation");
+  }
+  float box[3 * MMX_MPPI_MAX_ADIM] = {};
+  for (int k = 0; k < A; k++) box[k] = c->sigma[k], box[MMX_MPPI_MAX_ADIM + k] = c->low[k], box[2 * MMX_MPPI_MAX_ADIM + k] = c->high[k];
+  std::vector<int> src(n);
+  for (size_t i = 0; i < n; i++) src[i] = (int)(i / (size_t)P.K);
+  hipError_t e = hipMemcpy(p->box, box, sizeof(box), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(p->src, src.data(), n * sizeof(int), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    mmx_mppi_destroy(p);
+    return hip_check(sim, e, "mmx_mppi_create upload");
+  }
+  *out = p;
+  return MMX_OK;
+}
+
+void mmx_mppi_destroy(mmx_mppi* p) {
+  if (!p) return;
+  int prev = -1;
+  const bool sw = hipGetDevice(&prev) == hipSuccess && prev != p->device && hipSetDevice(p->device) == hipSuccess;
+  for (void* d : p->allocs) (void)hipFree(d);
+  if (sw) (void)hipSetDevice(prev);
+  delete p;
+}
+
+int mmx_mppi_reset(mmx_mppi* p, const float* action_dev) {
+  if (!p || !action_dev) return p ? fail(p->sim, MMX_EINVAL, "mmx_mppi_reset: NULL action") : MMX_EINVAL;
+  DeviceGuard guard(p->sim);
+  p->call = 0;
+  return hip_check(p->sim, mmx_launch_mppi_fill(&p->P, p->B.nominal, p->box, action_dev, p->sim->stream), "mmx_mppi_reset");
+}
+
+int mmx_mppi_plan(mmx_mppi* p, const void* snap_dev, int64_t rec_bytes, int32_t n_records, const float* xi_dev,
+                  float* action_out_dev) {
+  if (!p) return MMX_EINVAL;
+  mmx_sim* sim = p->sim;
+  if (!snap_dev || !action_out_dev || reinterpret_cast<uintptr_t>(snap_dev) % 16 != 0 ||
+      (rec_bytes != MMX_SNAPSHOT_BYTES && rec_bytes != MMX_SNAPSHOT_BYTES_CAMERAS) || n_records != p->P.M)
+    return fail(sim, MMX_EINVAL, "mmx_mppi_plan: bad arguments (NULL or unaligned blob, NULL output, not a record size, or "
+                                 "n_records != num_envs / samples)");
+  DeviceGuard guard(sim);
+  MppiParams P = p->P;
+  P.call_lo = (uint32_t)p->call, P.call_hi = (uint32_t)(p->call >> 32);
+  hipError_t e = mmx_launch_mppi_sample(&P, &p->B, p->box, xi_dev, sim->stream);
+  if (e == hipSuccess) e = mmx_launch_restore_strided(&sim->S, snap_dev, rec_bytes, n_records, p->src, nullptr, sim->stream);
+  if (e != hipSuccess) return hip_check(sim, e, "mmx_mppi_plan");
+  mmx_trajectory rec{};
+  rec.reward = p->B.reward;
+  rec.done = p->B.done;
+  const int rc = rollout_traj(sim, p->B.actions, P.A, 0, P.H, &rec, "mmx_mppi_plan");
+  if (rc != MMX_OK) return rc;
+  e = mmx_launch_mppi_update(&P, &p->B, p->box, action_out_dev, sim->stream);
+  if (e == hipSuccess) p->call++;
+  return hip_check(sim, e, "mmx_mppi_plan");
+}
+
+int mmx_mppi_reweight(mmx_mppi* p, float* action_out_dev) {
+  if (!p || !action_out_dev) return p ? fail(p->sim, MMX_EINVAL, "mmx_mppi_reweight: NULL output") : MMX_EINVAL;
+  DeviceGuard guard(p->sim);
+  return hip_check(p->sim, mmx_launch_mppi_update(&p->P, &p->B, p->box, action_out_dev, p->sim->stream), "mmx_mppi_reweight");
+}
+
+int mmx_mppi_get_buffers(mmx_mppi* p, mmx_mppi_buffers* out) {
+  if (!p || !out) return MMX_EINVAL;
+  const MppiBufs& B = p->B;
+  *out = mmx_mppi_buffers{B.nominal, B.noise, B.actions, B.reward, B.done, B.returns, B.weights, B.best};
+  return MMX_OK;
 }
 
 int mmx_queue_init(mmx_sim* sim, int32_t n_episodes, const uint64_t* seeds, const int32_t* tasks) {

@@ -1,6 +1,6 @@
 // The host seam between mmx_api.cpp and the kernel sources: every non-kernel extern "C" function that one
 // source defines and another calls, declared once.  mmx_api.cpp includes it and so does every source that
-// defines one of them (mmx_step.inc, mmx_render.hip, mmx_png.hip, mmx_snapshot.hip), so a parameter list
+// defines one of them (mmx_step.inc, mmx_render.hip, mmx_png.hip, mmx_snapshot.hip, mmx_mppi.hip), so a parameter list
 // changed on one side only is a compile error.  (The diagnostic exports that tools load through ctypes,
 // mmx_fsm_profile and mmx_render_clock among them, are not called across sources and are not listed.)
 #ifndef MMX_LAUNCH_H
@@ -8,6 +8,9 @@
 #include <hip/hip_runtime.h>
 
 #include "mmx_state.h"
+
+struct MppiParams;
+struct MppiBufs;
 
 extern "C" {
 
@@ -61,7 +64,17 @@ int64_t mmx_png_scratch_bytes(int width, int height);
 hipError_t mmx_launch_snapshot(const MMXState* S, void* blob, hipStream_t st);
 hipError_t mmx_launch_restore(const MMXState* S, const void* blob, int n_records, const int* src, unsigned char* mask,
                               hipStream_t st);
+// the same restore of records that lie rec_bytes apart (>= the sim's own record size: a camera-less sim reads
+// the fixed prefix of records taken with cameras); mmx_launch_restore is this at the sim's own record size
+hipError_t mmx_launch_restore_strided(const MMXState* S, const void* blob, int64_t rec_bytes, int n_records, const int* src,
+                                      unsigned char* mask, hipStream_t st);
 int64_t mmx_snapshot_record_bytes(int cameras);
+
+// mmx_mppi.hip (MppiParams, MppiBufs: mmx_mppi.h); box = device [3][MPPI_MAX_ADIM] sigma, low, high
+hipError_t mmx_launch_mppi_sample(const MppiParams* P, const MppiBufs* B, const float* box, const float* xi, hipStream_t st);
+hipError_t mmx_launch_mppi_update(const MppiParams* P, const MppiBufs* B, const float* box, float* action_out,
+                                  hipStream_t st);
+hipError_t mmx_launch_mppi_fill(const MppiParams* P, float* nominal, const float* box, const float* action, hipStream_t st);
 
 }  // extern "C"
 

@@ -134,10 +134,14 @@ extern "C" hipError_t mmx_launch_snapshot(const MMXState* S, void* blob, hipStre
                      static_cast<unsigned char*>(blob), rec_bytes);
   return hipGetLastError();
 }
+extern "C" hipError_t mmx_launch_restore_strided(const MMXState* S, const void* blob, int64_t rec_bytes, int n_records,
+                                                 const int* src, unsigned char* mask, hipStream_t st) {
+  if (rec_bytes < mmx_snapshot_record_bytes(S->rpose != nullptr) || rec_bytes % 16) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(mmx_restore_kernel, dim3((S->N + kWaves - 1) / kWaves), dim3(64 * kWaves), 0, st, *S,
+                     static_cast<const unsigned char*>(blob), (size_t)rec_bytes, n_records, src, mask);
+  return hipGetLastError();
+}
 extern "C" hipError_t mmx_launch_restore(const MMXState* S, const void* blob, int n_records, const int* src,
                                          unsigned char* mask, hipStream_t st) {
-  const size_t rec_bytes = (size_t)mmx_snapshot_record_bytes(S->rpose != nullptr);
-  hipLaunchKernelGGL(mmx_restore_kernel, dim3((S->N + kWaves - 1) / kWaves), dim3(64 * kWaves), 0, st, *S,
-                     static_cast<const unsigned char*>(blob), rec_bytes, n_records, src, mask);
-  return hipGetLastError();
+  return mmx_launch_restore_strided(S, blob, mmx_snapshot_record_bytes(S->rpose != nullptr), n_records, src, mask, st);
 }

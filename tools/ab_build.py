@@ -22,12 +22,14 @@ def one(spec):
         name, rev = spec.split(":")[0].split("@")
         tmp = tempfile.mkdtemp(prefix=f"mmx_{name}_")
         subprocess.check_call(f"git -C {REPO} archive {rev} mujoco_manip_amd/csrc include | tar -x -C {tmp}", shell=True)
-        saved = _build.CSRC
+        saved = _build.CSRC, _build.SOURCES
         _build.CSRC = os.path.join(tmp, "mujoco_manip_amd", "csrc")
+        # (a source added since REV, mmx_mppi.hip for one, is not part of that revision's library)
+        _build.SOURCES = [s for s in _build.SOURCES if os.path.exists(os.path.join(_build.CSRC, s))]
         try:
             return _build.build_variant(out, defs, profile=prof)
         finally:
-            _build.CSRC = saved
+            _build.CSRC, _build.SOURCES = saved
     return _build.build_variant(out, defs, profile=prof)
 
 
