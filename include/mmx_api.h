@@ -301,6 +301,74 @@ int  mmx_mppi_get_buffers(mmx_mppi* p, mmx_mppi_buffers* out);
  * stays.  Asynchronous on the planner sim's stream; MMX_EINVAL for a NULL planner or output. */
 int  mmx_mppi_reweight(mmx_mppi* p, float* action_out_dev);
 
+/* Closed-loop MLP policies inside the fused step launches (no reference counterpart: the reference steps one env
+ * per process from Python, so a learned policy there is a torch call between two env.step() calls; here the env's
+ * own wave evaluates a_t = pi(obs_t) between two env steps of one launch and the observation never leaves the
+ * device).  The network is a multi-layer perceptron on the numeric observation [85]:
+ *     x = (obs - obs_shift) * obs_scale            (a scale of 0 drops an entry)
+ *     h_l = act(W_l h_{l-1} + b_l), l < n_layers - 1;   mean = W_last h + b_last        (fp32; one accumulator per
+ *     neuron that starts at the bias and adds the inputs in ascending order with fused multiply-adds; tanh as
+ *     1 - 2 / (1 + exp2(2 x log2 e)) with the hardware's exp2 and reciprocal, within 8 * 2^-24 of tanh, exactly +-1
+ *     for |x| >= 23 and 0 at 0)
+ *     action[a] = clamp(mean[a] + exp(log_std[a]) z[a], low[a], high[a])
+ * z is the draw of mmx_mppi_plan's step 1: element (rollout step t, env i, component a) of call `call` under the
+ * policy's seed is Philox4x32-10 with key = seed and counter = (call low, call high, i, 4 t + a / 4), Box-Muller on
+ * its outputs; it depends on (seed, call, t, i, a) alone, never on lanes or the launch plan.
+ * mmx_policy_config: every pointer is a HOST pointer, read during mmx_policy_create only.  n_layers in 1 ..
+ * MMX_POLICY_MAX_LAYERS linear layers (1: a linear policy); width[l] in 1 .. MMX_POLICY_MAX_WIDTH = the outputs of
+ * layer l, the last one the action dimension (<= MMX_MPPI_MAX_ADIM) of the sims the policy will drive; activation
+ * after every layer but the last; weight[l] row-major [width[l]][inputs] (torch.nn.Linear.weight), inputs = 85 for
+ * l = 0 and width[l - 1] after; bias[l] [width[l]] or NULL (0); obs_shift, obs_scale [85] or NULL (0, 1); log_std
+ * [A] or NULL (deterministic: action = clamp(mean)); low, high [A] or NULL (no clamp).
+ * mmx_policy_create copies everything to the sim's device once (weights transposed and padded for the kernel's
+ * coalesced reads, exp(log_std) evaluated on the host) and allocates nothing afterwards; MMX_EINVAL, with nothing
+ * allocated, for a NULL argument, n_layers outside 1 .. 4, a width outside 1 .. 256, a last width above
+ * MMX_MPPI_MAX_ADIM, a NULL weight[l] or an unknown activation.  mmx_policy_destroy frees it (before mmx_destroy
+ * of the creating sim, after the last launch that uses it has run).
+ * mmx_policy_eval: the network alone, mean_out_dev [n][A] from obs_dev [n][85] (device pointers; one wave per
+ * row), asynchronous on the creating sim's stream: behaviour-cloning validation on dataset observations.
+ * MMX_EINVAL for a NULL argument or n < 0; n == 0 does nothing.
+ * mmx_rollout_policy: n_env_steps env steps of every env of `sim` in the fused launches of mmx_rollout_actions
+ * (lanes, launch plan, dispatch order, both camera paths), the action of rollout step t and env i computed from
+ * the observation that env holds before the step (the sim's obs buffer: after an autoreset the new episode's first
+ * observation) and written to prec->actions[t][i][0 .. A) (device, [T][N][A], required); prec->mean (the network's
+ * output) and prec->noise (z; 0 for a deterministic policy) are optional, same shape.  rec: the per-step record of
+ * mmx_rollout_actions, may be NULL.  call: the caller increments it per call for fresh noise.  With cameras the
+ * policy still reads the numeric observation only.
+ * Contract: afterwards every sim-owned buffer and every slice of rec is bit for bit what mmx_rollout_actions(sim,
+ * prec->actions, A, n_env_steps, rec) gives from the same starting state.
+ * n_env_steps == 0 returns MMX_OK; MMX_EINVAL, with nothing launched, for a NULL sim, policy, prec or
+ * prec->actions, n_env_steps < 0, a policy whose action width is not the sim's action dimension, and a policy
+ * created on another device. */
+#define MMX_POLICY_MAX_LAYERS 4
+#define MMX_POLICY_MAX_WIDTH 256
+#define MMX_POLICY_TANH 0
+#define MMX_POLICY_RELU 1
+typedef struct mmx_policy mmx_policy;
+typedef struct {
+  int32_t n_layers;
+  int32_t width[MMX_POLICY_MAX_LAYERS];
+  int32_t activation;   /* MMX_POLICY_TANH, MMX_POLICY_RELU */
+  const float* weight[MMX_POLICY_MAX_LAYERS];
+  const float* bias[MMX_POLICY_MAX_LAYERS];
+  const float* obs_shift;
+  const float* obs_scale;
+  const float* log_std;
+  const float* low;
+  const float* high;
+  uint64_t seed;
+} mmx_policy_config;
+typedef struct {        /* caller-owned device arrays [T][N][A] */
+  float* actions;       /* required: the actions the envs were stepped with */
+  float* mean;          /* NULL, or the network's output before noise and clamp */
+  float* noise;         /* NULL, or z */
+} mmx_policy_record;
+int  mmx_policy_create(mmx_sim* sim, const mmx_policy_config* cfg, mmx_policy** out);
+void mmx_policy_destroy(mmx_policy* p);
+int  mmx_policy_eval(mmx_policy* p, const float* obs_dev, int32_t n, float* mean_out_dev);
+int  mmx_rollout_policy(mmx_sim* sim, mmx_policy* policy, int32_t n_env_steps, uint64_t call,
+                        const mmx_policy_record* prec, const mmx_trajectory* rec);
+
 /* Batched PNG encoder (dataset emission, generate_dataset.py:250-260: LeRobot embeds image
  * features as PNG files).  Encodes n RGB8 images (device, image i at rgb_dev + i * img_stride,
  * rows of 3 * width bytes, height <= 1024, width <= MMX_PNG_MAX_WIDTH: the encoder's row-above match

@@ -7,7 +7,7 @@ environments in lockstep by HIP kernels (libmmx.so, C-ABI in include/mmx_api.h).
 """
 from .constants import ACTION_REPEAT, ALL_TASKS, BINS, OBJECTS, TASK_SETS  # noqa: F401
 
-__all__ = ["PickPlaceVecEnv", "PickPlaceGymEnv", "Snapshot", "MppiPlanner", "build_library", "episode_seed"]
+__all__ = ["PickPlaceVecEnv", "PickPlaceGymEnv", "Snapshot", "MppiPlanner", "MlpPolicy", "build_library", "episode_seed"]
 
 
 def build_library(force: bool = False) -> str:
@@ -35,6 +35,10 @@ def __getattr__(name):
         from .planner import MppiPlanner
 
         return MppiPlanner
+    if name == "MlpPolicy":
+        from .policy import MlpPolicy
+
+        return MlpPolicy
     if name == "PickPlaceGymEnv":
         from .gym_env import PickPlaceGymEnv
 

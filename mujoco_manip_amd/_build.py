@@ -15,7 +15,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libmmx.so")
 LIB_PROF = os.path.join(PKG, "libmmx_prof.so")
 SOURCES = ["mmx_kernels.hip", "mmx_step_l192.hip", "mmx_render.hip", "mmx_render_lit.hip", "mmx_png.hip",
-           "mmx_snapshot.hip", "mmx_mppi.hip", "mmx_api.cpp"]
+           "mmx_snapshot.hip", "mmx_mppi.hip", "mmx_policy.hip", "mmx_api.cpp"]
 ARCH = os.environ.get("MMX_OFFLOAD_ARCH", "gfx950")
 # device-code math: x / y as x * rcp(y) and sqrt without the denormal-scaling wrapper (v_rcp_f32 /
 # v_sqrt_f32, <= 1 ulp) instead of the correctly rounded fdiv / sqrt expansions (~10 VALU each).

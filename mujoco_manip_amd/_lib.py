@@ -99,6 +99,26 @@ class MMXMppiBuffers(C.Structure):
     ]
 
 
+# include/mmx_api.h MMX_POLICY_MAX_LAYERS, MMX_POLICY_MAX_WIDTH, MMX_POLICY_TANH / MMX_POLICY_RELU
+POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 4, 256
+POLICY_ACTIVATIONS = ("tanh", "relu")
+
+
+class MMXPolicyConfig(C.Structure):
+    """mmx_policy_config (include/mmx_api.h): host pointers, read during mmx_policy_create."""
+    _fields_ = [
+        ("n_layers", C.c_int32), ("width", C.c_int32 * POLICY_MAX_LAYERS), ("activation", C.c_int32),
+        ("weight", C.c_void_p * POLICY_MAX_LAYERS), ("bias", C.c_void_p * POLICY_MAX_LAYERS),
+        ("obs_shift", C.c_void_p), ("obs_scale", C.c_void_p), ("log_std", C.c_void_p), ("low", C.c_void_p),
+        ("high", C.c_void_p), ("seed", C.c_uint64),
+    ]
+
+
+class MMXPolicyRecord(C.Structure):
+    """mmx_policy_record (include/mmx_api.h): caller-owned device arrays [T][N][A]; actions is required."""
+    _fields_ = [("actions", C.c_void_p), ("mean", C.c_void_p), ("noise", C.c_void_p)]
+
+
 # per-env width and dtype of every trajectory array
 TRAJ_FIELDS = {"obs": (NOBS, "float32"), "reward": (1, "float32"), "done": (3, "int32"),
                "reward_components": (6, "float32"), "target": (4, "float32"), "episode_i": (EPI_N, "int32"),
@@ -158,6 +178,10 @@ _PROTOS = {
     "mmx_mppi_plan": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp]),
     "mmx_mppi_get_buffers": (C.c_int, [_vp, C.POINTER(MMXMppiBuffers)]),
     "mmx_mppi_reweight": (C.c_int, [_vp, _vp]),
+    "mmx_policy_create": (C.c_int, [_vp, C.POINTER(MMXPolicyConfig), C.POINTER(_vp)]),
+    "mmx_policy_destroy": (None, [_vp]),
+    "mmx_policy_eval": (C.c_int, [_vp, _vp, _i32, _vp]),
+    "mmx_rollout_policy": (C.c_int, [_vp, _vp, _i32, C.c_uint64, C.POINTER(MMXPolicyRecord), C.POINTER(MMXTrajectory)]),
     "mmx_png_bound": (_i64, [_i32, _i32]),
     "mmx_png_scratch": (_i64, [_i32, _i32]),
     "mmx_png_encode": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
@@ -198,6 +222,7 @@ EXPORTED = tuple(_PROTOS)
 _SINCE_BUDGET = ("mmx_set_rollout_budget", "mmx_rollout_budget", "mmx_rollout_step_counts")
 _SINCE_MPPI = ("mmx_mppi_create", "mmx_mppi_destroy", "mmx_mppi_reset", "mmx_mppi_plan", "mmx_mppi_get_buffers",
                "mmx_mppi_reweight")
+_SINCE_POLICY = ("mmx_policy_create", "mmx_policy_destroy", "mmx_policy_eval", "mmx_rollout_policy")
 
 _lib = None
 
@@ -216,7 +241,7 @@ def load(build_if_missing: bool = True):
         _build.build(profile=profile)
     L = C.CDLL(path)
     for name, (restype, argtypes) in _PROTOS.items():
-        if name in _SINCE_BUDGET + _SINCE_MPPI and os.environ.get("MMX_LIB_PATH") and not hasattr(L, name):
+        if name in _SINCE_BUDGET + _SINCE_MPPI + _SINCE_POLICY and os.environ.get("MMX_LIB_PATH") and not hasattr(L, name):
             continue
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
@@ -687,3 +712,55 @@ class Mppi:
         dev = f"cuda:{self.sim.cfg.device}"
         return {n: torch.as_tensor(_DevArray(getattr(self.buffers, n), shp, t, self), device=dev)
                 for n, (shp, t) in shapes.items()}
+
+
+class Policy:
+    """Owner of one mmx_policy on the device of `sim` (mmx_policy_* of include/mmx_api.h): an MLP on the numeric
+    observation.  layers: [(W [out, in], b [out] or None), ...] float32 numpy arrays; the other arrays float32 or
+    None.  Close it before the sim."""
+
+    def __init__(self, sim: Sim, layers, activation: int, obs_shift=None, obs_scale=None, log_std=None, low=None,
+                 high=None, seed: int = 0):
+        cfg = MMXPolicyConfig(n_layers=len(layers), activation=int(activation), seed=int(seed) & (2**64 - 1))
+        keep = []  # the host arrays, alive during the call
+
+        def ptr(a):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, np.float32)
+            keep.append(a)
+            return a.ctypes.data
+
+        for k, (W, b) in enumerate(layers[:POLICY_MAX_LAYERS]):
+            cfg.width[k] = int(np.shape(W)[0])
+            cfg.weight[k], cfg.bias[k] = ptr(W), ptr(b)
+        cfg.obs_shift, cfg.obs_scale, cfg.log_std = ptr(obs_shift), ptr(obs_scale), ptr(log_std)
+        cfg.low, cfg.high = ptr(low), ptr(high)
+        self.sim, self.L = sim, sim.L
+        self.action_dim = int(np.shape(layers[-1][0])[0]) if layers else 0
+        out = C.c_void_p()
+        rc = self.L.mmx_policy_create(sim.ptr, C.byref(cfg), C.byref(out))
+        if rc != 0 or not out.value:
+            raise ValueError(f"mmx_policy_create failed ({rc}): {self.L.mmx_last_error(sim.ptr).decode()}")
+        self.ptr = out
+
+    def close(self):
+        if getattr(self, "ptr", None) is not None and self.ptr.value:
+            self.L.mmx_policy_destroy(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def eval(self, obs_ptr: int, n: int, out_ptr: int):
+        """mean [n][A] at out_ptr of the observations [n][85] at obs_ptr (device pointers; mmx_policy_eval,
+        asynchronous on the creating sim's stream)."""
+        self.sim._check(self.L.mmx_policy_eval(self.ptr, C.c_void_p(obs_ptr), int(n), C.c_void_p(out_ptr)), "mmx_policy_eval")
+
+    def rollout(self, sim: Sim, n_env_steps: int, call: int, prec: MMXPolicyRecord, record: MMXTrajectory | None = None):
+        """n_env_steps closed-loop env steps of `sim` under this policy in fused launches (mmx_rollout_policy)."""
+        sim._check(self.L.mmx_rollout_policy(sim.ptr, self.ptr, int(n_env_steps), int(call) & (2**64 - 1), C.byref(prec),
+                                             None if record is None else C.byref(record)), "mmx_rollout_policy")

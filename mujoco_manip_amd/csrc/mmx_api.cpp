@@ -19,6 +19,7 @@
 #include "mmx_launch.h"
 #include "mmx_mppi.h"
 #include "mmx_plan.h"
+#include "mmx_policy.h"
 #include "mmx_seed.h"
 #include "mmx_state.h"
 
@@ -102,6 +103,15 @@ struct mmx_mppi {
   int* src = nullptr;    // [N]
   uint64_t call = 0;
   std::vector<void*> allocs;
+};
+
+// An MLP policy on the device of the sim it was created with: the launch parameters and its one device
+// allocation (the packed weights and vectors, mmx_policy.h), freed by mmx_policy_destroy
+struct mmx_policy {
+  mmx_sim* sim = nullptr;
+  int device = 0;  // the sim's (kept for mmx_policy_destroy and mmx_rollout_policy's check)
+  MmxPolicy P{};
+  float* data = nullptr;
 };
 
 namespace {
@@ -431,10 +441,11 @@ struct StepLaunchers {
   decltype(&mmx_launch_step) step;
   decltype(&mmx_launch_traj) traj;
   decltype(&mmx_launch_physics) physics;
+  decltype(&mmx_launch_policy) policy;
 };
 StepLaunchers step_launchers(const mmx_sim* sim) {
-  return sim->step_rows == 192 ? StepLaunchers{mmx_launch_step_l192, mmx_launch_traj_l192, mmx_launch_physics_l192}
-                               : StepLaunchers{mmx_launch_step, mmx_launch_traj, mmx_launch_physics};
+  return sim->step_rows == 192 ? StepLaunchers{mmx_launch_step_l192, mmx_launch_traj_l192, mmx_launch_physics_l192, mmx_launch_policy_l192}
+                               : StepLaunchers{mmx_launch_step, mmx_launch_traj, mmx_launch_physics, mmx_launch_policy};
 }
 // floats per env that each action mode's action needs
 constexpr int kDim[5] = {4, 8, 10, 8, 10};
@@ -981,6 +992,82 @@ int mmx_mppi_get_buffers(mmx_mppi* p, mmx_mppi_buffers* out) {
   const MppiBufs& B = p->B;
   *out = mmx_mppi_buffers{B.nominal, B.noise, B.actions, B.reward, B.done, B.returns, B.weights, B.best};
   return MMX_OK;
+}
+
+// MLP policies (mmx_policy.h; mmx_policy.hip, mmx_env_policy_kernel of mmx_step.inc)
+int mmx_policy_create(mmx_sim* sim, const mmx_policy_config* c, mmx_policy** out) {
+  if (out) *out = nullptr;
+  if (!sim || !c || !out) return sim ? fail(sim, MMX_EINVAL, "mmx_policy_create: NULL argument") : MMX_EINVAL;
+  bool ok = c->n_layers >= 1 && c->n_layers <= MMX_POLICY_MAX_LAYERS &&
+            (c->activation == MMX_POLICY_TANH || c->activation == MMX_POLICY_RELU);
+  for (int l = 0; l < c->n_layers && ok; l++) ok = c->width[l] >= 1 && c->width[l] <= MMX_POLICY_MAX_WIDTH && c->weight[l];
+  ok = ok && c->width[c->n_layers - 1] <= MMX_MPPI_MAX_ADIM;
+  if (!ok)
+    return fail(sim, MMX_EINVAL, "mmx_policy_create: n_layers outside 1..4, a width outside 1..256, a last width above 10, a NULL "
+                                 "weight or an unknown activation");
+  mmx_policy* p = new (std::nothrow) mmx_policy();
+  if (!p) return fail(sim, MMX_ENOMEM, "mmx_policy_create: host allocation");
+  p->sim = sim;
+  p->device = sim->cfg.device;
+  MmxPolicy& P = p->P;
+  P.n_layers = c->n_layers;
+  P.activation = c->activation;
+  for (int l = 0; l < c->n_layers; l++) P.in[l] = l ? c->width[l - 1] : MMX_NOBS, P.out[l] = c->width[l];
+  P.A = c->width[c->n_layers - 1];
+  P.stochastic = c->log_std != nullptr;
+  P.seed_lo = (uint32_t)c->seed, P.seed_hi = (uint32_t)(c->seed >> 32);
+  std::vector<float> blob(policy_layout(P));
+  policy_pack(P, c->weight, c->bias, c->obs_shift, c->obs_scale, c->log_std, c->low, c->high, blob.data());
+  DeviceGuard guard(sim);
+  void* d = nullptr;
+  if (hipMalloc(&d, blob.size() * sizeof(float)) != hipSuccess) {
+    delete p;
+    return fail(sim, MMX_ENOMEM, "mmx_policy_create: device allocation");
+  }
+  p->data = static_cast<float*>(d);
+  P.data = p->data;
+  const hipError_t e = hipMemcpy(d, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    mmx_policy_destroy(p);
+    return hip_check(sim, e, "mmx_policy_create upload");
+  }
+  *out = p;
+  return MMX_OK;
+}
+
+void mmx_policy_destroy(mmx_policy* p) {
+  if (!p) return;
+  int prev = -1;
+  const bool sw = hipGetDevice(&prev) == hipSuccess && prev != p->device && hipSetDevice(p->device) == hipSuccess;
+  if (p->data) (void)hipFree(p->data);
+  if (sw) (void)hipSetDevice(prev);
+  delete p;
+}
+
+int mmx_policy_eval(mmx_policy* p, const float* obs_dev, int32_t n, float* mean_out_dev) {
+  if (!p) return MMX_EINVAL;
+  if (!obs_dev || !mean_out_dev || n < 0) return fail(p->sim, MMX_EINVAL, "mmx_policy_eval: NULL argument or n < 0");
+  DeviceGuard guard(p->sim);
+  return hip_check(p->sim, mmx_launch_policy_eval(&p->P, obs_dev, n, mean_out_dev, p->sim->stream), "mmx_policy_eval");
+}
+
+int mmx_rollout_policy(mmx_sim* sim, mmx_policy* policy, int32_t n_env_steps, uint64_t call, const mmx_policy_record* prec,
+                       const mmx_trajectory* rec) {
+  if (!sim || !policy || !prec || !prec->actions || n_env_steps < 0)
+    return sim ? fail(sim, MMX_EINVAL, "mmx_rollout_policy: bad arguments (NULL policy or actions, or n_env_steps < 0)") : MMX_EINVAL;
+  if (policy->P.A != kDim[sim->S.action_mode])
+    return fail(sim, MMX_EINVAL, "mmx_rollout_policy: the policy's action width is not the sim's action dimension");
+  if (policy->device != sim->cfg.device) return fail(sim, MMX_EINVAL, "mmx_rollout_policy: the policy was created on another device");
+  MMXTraj R{};
+  if (rec) R = MMXTraj{rec->obs, rec->reward, rec->done, rec->reward_components, rec->target, rec->episode_i, rec->qpos, rec->qvel};
+  MmxPolicy P = policy->P;
+  P.call_lo = (uint32_t)call, P.call_hi = (uint32_t)(call >> 32);
+  const MMXPolicyRec PR{prec->actions, prec->mean, prec->noise};
+  const auto launch = step_launchers(sim).policy;
+  return rollout(sim, n_env_steps, "mmx_rollout_policy", false,
+                 [&](const MMXState* S, int base, int count, int ns, int k0, hipStream_t st, const int* ord, const MMXBudget*) {
+                   return launch(S, &R, &P, &PR, base, count, ns, k0, st, ord);
+                 });
 }
 
 int mmx_queue_init(mmx_sim* sim, int32_t n_episodes, const uint64_t* seeds, const int32_t* tasks) {

@@ -1,6 +1,6 @@
 // The host seam between mmx_api.cpp and the kernel sources: every non-kernel extern "C" function that one
 // source defines and another calls, declared once.  mmx_api.cpp includes it and so does every source that
-// defines one of them (mmx_step.inc, mmx_render.hip, mmx_png.hip, mmx_snapshot.hip, mmx_mppi.hip), so a parameter list
+// defines one of them (mmx_step.inc, mmx_render.hip, mmx_png.hip, mmx_snapshot.hip, mmx_mppi.hip, mmx_policy.hip), so a parameter list
 // changed on one side only is a compile error.  (The diagnostic exports that tools load through ctypes,
 // mmx_fsm_profile and mmx_render_clock among them, are not called across sources and are not listed.)
 #ifndef MMX_LAUNCH_H
@@ -11,6 +11,8 @@
 
 struct MppiParams;
 struct MppiBufs;
+struct MmxPolicy;
+struct MMXPolicyRec;
 
 extern "C" {
 
@@ -20,7 +22,9 @@ extern "C" {
                                   int nsteps, hipStream_t st, const int* order);                                       \
   hipError_t mmx_launch_traj##sfx(const MMXState* S, const MMXTraj* R, const float* actions, int adim, int expert,     \
                                   int base, int count, int nsteps, int k0, hipStream_t st, const int* order);          \
-  hipError_t mmx_launch_physics##sfx(const MMXState* S, int n, int with_ik, hipStream_t st);
+  hipError_t mmx_launch_physics##sfx(const MMXState* S, int n, int with_ik, hipStream_t st);                           \
+  hipError_t mmx_launch_policy##sfx(const MMXState* S, const MMXTraj* R, const MmxPolicy* P, const MMXPolicyRec* PR,   \
+                                    int base, int count, int nsteps, int k0, hipStream_t st, const int* order);
 MMX_DECLARE_STEP_LAUNCHERS()
 MMX_DECLARE_STEP_LAUNCHERS(_l192)
 #undef MMX_DECLARE_STEP_LAUNCHERS
@@ -75,6 +79,9 @@ hipError_t mmx_launch_mppi_sample(const MppiParams* P, const MppiBufs* B, const 
 hipError_t mmx_launch_mppi_update(const MppiParams* P, const MppiBufs* B, const float* box, float* action_out,
                                   hipStream_t st);
 hipError_t mmx_launch_mppi_fill(const MppiParams* P, float* nominal, const float* box, const float* action, hipStream_t st);
+
+// mmx_policy.hip (MmxPolicy, MMXPolicyRec: mmx_policy.h): the network alone on n observation rows, one wave each
+hipError_t mmx_launch_policy_eval(const MmxPolicy* P, const float* obs, int n, float* mean_out, hipStream_t st);
 
 }  // extern "C"
 

@@ -38,6 +38,7 @@
 #include "mmx_geom.h"
 #include "mmx_state.h"
 #include "mmx_launch.h"
+#include "mmx_policy.h"
 
 #define WG 64  // lanes of the wave that runs a phase
 // lane within the wave (a workgroup is one wave: one env)
@@ -3531,6 +3532,97 @@ MMX_NO_TAIL_MARK MMX_STEP_SYM(mmx_env_traj_kernel)(MMXState S, MMXTraj R, const 
   }
 }
 
+// The policy's action for the env step that follows (mmx_env_policy_kernel), on the env's wave, out of line like
+// the substep.  The observation comes from S.obs[i] in HBM, not from the LDS copy: at the launch's first step
+// that copy does not exist, and after an autoreset S.obs holds the new episode's first observation, which is
+// what a loop of obs -> policy -> step() feeds the policy.  Before step_begin the whole scratch region is
+// free: the normalised input sits at its start, then the two activation buffers.  Lane 0 adds the noise, clamps
+// and writes the action row itself; step_begin's lane 0 then reads its own stores back (traj_record's
+// argument for the reward), so the row is never handed across lanes through global memory.  No workgroup
+// barrier: the helper wave (192 rows) waits at the record-load barrier meanwhile.
+#define POL_X 0
+#define POL_B0 ((POLICY_NOBS + 3) & ~3)
+#define POL_B1 (POL_B0 + POLICY_MAX_WIDTH)
+static_assert(POL_B1 + POLICY_MAX_WIDTH <= SCR_FLOATS && POLICY_NOBS == MMX_NOBS, "the policy's scratch exceeds the scratch region");
+__device__ __attribute__((noinline)) void policy_act(const MMXState& S, const MmxPolicy& P, const MMXPolicyRec& PR, int i,
+                                                     unsigned step) {
+  float* scr = scr_of(g_E);
+  const float* data = policy_data(P);
+  const float* obs = S.obs + (size_t)i * MMX_NOBS;
+  const int shift_off = policy_u(P.shift_off), scale_off = policy_u(P.scale_off);
+  for (int k = LANE; k < MMX_NOBS; k += WG) scr[POL_X + k] = policy_normalise(obs[k], data[shift_off + k], data[scale_off + k]);
+  SYNC();
+  const float* mean = policy_forward_wave(P, data, scr + POL_X, scr + POL_B0, scr + POL_B1, LANE);
+  if (LANE == 0) {
+    const int A = P.A;
+    const size_t row = ((size_t)step * (size_t)S.N + (size_t)i) * (size_t)A;
+    const float *std = data + P.std_off, *low = data + P.low_off, *high = data + P.high_off;
+    for (int a = 0; a < A; a++) {
+      const float m = mean[a];
+      float z = 0.f, act = mppi_clamp(m, low[a], high[a]);
+      if (P.stochastic) {
+        z = mppi_draw(P.seed_lo, P.seed_hi, P.call_lo, P.call_hi, step, (uint32_t)i, (uint32_t)a);
+        act = policy_action(m, std[a], z, low[a], high[a]);
+      }
+      PR.actions[row + a] = act;
+      if (PR.mean) PR.mean[row + a] = m;
+      if (PR.noise) PR.noise[row + a] = z;
+    }
+  }
+}
+
+// mmx_env_traj_kernel's step loop with the action of every step computed by an MLP policy from the env's own
+// observation, inside the launch (mmx_rollout_policy): step k of the launch is the rollout's step k0 + k; before
+// step_begin the env's wave evaluates the policy (policy_act) and writes the action row [k0 + k][i] of
+// PR.actions, which step_begin then reads as the trajectory kernel reads a given row.  Everything else is that
+// kernel's body, so states and records are bit for bit what mmx_rollout_actions gives on the recorded actions.
+// A kernel of its own with its own copy of the helper wave's loop (sharing the loop reschedules the existing
+// 192-row kernels); policy_act adds no workgroup barrier, so the helper's barrier sequence is unchanged.
+extern "C" __global__ void __launch_bounds__(MMX_STEP_THREADS) __attribute__((amdgpu_waves_per_eu(MMX_STEP_WAVES, MMX_STEP_WAVES)))
+MMX_NO_TAIL_MARK MMX_STEP_SYM(mmx_env_policy_kernel)(MMXState S, MMXTraj R, MmxPolicy P, MMXPolicyRec PR, int base, int nsteps,
+                                    int k0, const int* order) {
+  const int i = order ? order[blockIdx.x] : base + blockIdx.x;
+  if (i >= S.N) return;
+#if MMX_STEP_HELPER
+  if (threadIdx.x >= 64) {  // the helper wave, as in mmx_env_traj_kernel
+    for (int k = 0; k < nsteps; k++) {
+      if (k) {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        XSYNC();
+      }
+      XSYNC();  // step_begin's record load (the env wave runs the policy before it)
+      for (int sub = 0; sub < MMX_NSUBSTEP; sub++) {  // mj_step_wave's barriers C, K, A, P, Q
+        __syncthreads();
+        DELAY_HELPER();
+        ik_wave(g_E);
+        __syncthreads();  // K: the IK has read the kinematics cache; the env wave may overwrite it
+        __syncthreads();
+        DELAY_HELPER();
+        dynamics_wave(g_E);
+        __syncthreads();
+        collide_pairs(g_E, false, 2);
+        __syncthreads();
+      }
+    }
+    return;
+  }
+#endif
+  for (int k = 0; k < nsteps; k++) {
+    if (k) {  // the previous step's record and observation stores complete before this step reads them
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+      XSYNC();
+    }
+    const size_t step = (size_t)(k0 + k);
+    policy_act(S, P, PR, i, (unsigned)step);
+    step_begin(S, i, PR.actions + step * (size_t)S.N * (size_t)P.A, P.A, 0);
+    XSYNC();
+    for (int sub = 0; sub < MMX_NSUBSTEP; sub++)
+      substep(S.solver_max_iter, S.solver_tol, sub == MMX_NSUBSTEP - 1 ? contacts_dst(S, i) : nullptr);
+    step_finish(S, i);
+    traj_record(S, R, i, step * (size_t)S.N + (size_t)i);
+  }
+}
+
 // One IK + mj_step substep per launch (mmx_launch_physics, the physics-level harness of mmx_physics_step;
 // with SS_GYM the env step's first / last), in the build's own layout like the step kernels above.  With
 // the helper wave (192 rows), threads 64..127 run one substep of mmx_env_step_kernel's helper loop: the
@@ -3636,5 +3728,15 @@ extern "C" hipError_t MMX_STEP_SYM(mmx_launch_traj)(const MMXState* S, const MMX
   if (count <= 0 || nsteps <= 0) return hipSuccess;
   hipLaunchKernelGGL(MMX_STEP_SYM(mmx_env_traj_kernel), dim3(count), dim3(MMX_STEP_THREADS), step_lds_pad(), st, *S, *R, actions, adim,
                      expert, base, nsteps, k0, order);
+  return hipGetLastError();
+}
+// `nsteps` env steps of envs [base, base+count) from the rollout's step k0 on, every action from the policy P
+extern "C" hipError_t MMX_STEP_SYM(mmx_launch_policy)(const MMXState* S, const MMXTraj* R, const MmxPolicy* P,
+                                                      const MMXPolicyRec* PR, int base, int count, int nsteps, int k0,
+                                                      hipStream_t st, const int* order) {
+  if (count <= 0 || nsteps <= 0) return hipSuccess;
+  if (!PR->actions || !P->data) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(MMX_STEP_SYM(mmx_env_policy_kernel), dim3(count), dim3(MMX_STEP_THREADS), step_lds_pad(), st, *S, *R, *P, *PR,
+                     base, nsteps, k0, order);
   return hipGetLastError();
 }

@@ -1,0 +1,136 @@
+"""MlpPolicy — a learned policy a_t = pi(obs_t) evaluated inside the fused step launches (mmx_rollout_policy,
+include/mmx_api.h): the env's own wave runs the network between two env steps, so a closed-loop rollout makes
+no launch, and no host round trip, per env step.
+
+The network is a multi-layer perceptron on the flat numeric observation [85] (vec_env.split_obs names its
+slices): x = (obs - obs_shift) * obs_scale, up to four linear layers of at most 256 outputs with tanh or ReLU
+between them, and action = clip(mean + exp(log_std) * z, low, high) with z a counter-based normal draw that
+depends on (seed, call, step, env, component) alone (log_std None: deterministic).
+
+    policy = MlpPolicy.from_torch(net, obs_shift=mu, obs_scale=1 / sd)     # net: nn.Sequential(Linear, Tanh, ...)
+    policy.bind(env)
+    out = env.rollout_policy(policy, n_steps=100)          # {"obs", "reward", "done", "actions"}: [T, N, ...]
+    mean = policy.eval(dataset_obs)                        # the network alone, for behaviour-cloning validation
+    policy.close()                                         # before env.close()
+
+This module imports without a GPU; bind() needs one.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _lib
+
+ACTIVATIONS = _lib.POLICY_ACTIVATIONS
+
+
+def _f32(a, name: str, shape=None):
+    """A float32 numpy copy of a numpy array, a torch tensor or a sequence; `shape`: the shape it must have."""
+    if a is None:
+        return None
+    if hasattr(a, "detach"):  # a torch tensor, on any device
+        a = a.detach().cpu().numpy()
+    a = np.array(a, dtype=np.float32)
+    if shape is not None and a.shape != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}, got {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+class MlpPolicy:
+    def __init__(self, layers, activation: str = "tanh", obs_shift=None, obs_scale=None, log_std=None, low=None,
+                 high=None, seed: int = 0):
+        """layers: [(W [out, in], b [out] or None), ...], W as torch.nn.Linear.weight; the first layer reads the 85
+        observation entries, the last one's outputs are the action.  low / high None: the action mode's box
+        (planner.action_box) once bound, where it has one."""
+        layers = list(layers)
+        if not 1 <= len(layers) <= _lib.POLICY_MAX_LAYERS:
+            raise ValueError(f"a policy has 1 to {_lib.POLICY_MAX_LAYERS} linear layers, got {len(layers)}")
+        if activation not in ACTIVATIONS:
+            raise ValueError(f"activation must be one of {ACTIVATIONS}, got '{activation}'")
+        self.layers, n_in = [], _lib.NOBS
+        for k, layer in enumerate(layers):
+            W, b = layer if isinstance(layer, (tuple, list)) else (layer, None)
+            W = _f32(W, f"layers[{k}] weight")
+            if W.ndim != 2 or W.shape[1] != n_in:
+                raise ValueError(f"layers[{k}] weight must be [out, {n_in}], got {W.shape}")
+            if not 1 <= W.shape[0] <= _lib.POLICY_MAX_WIDTH:
+                raise ValueError(f"layers[{k}] has {W.shape[0]} outputs; a layer has 1 to {_lib.POLICY_MAX_WIDTH}")
+            self.layers.append((W, _f32(b, f"layers[{k}] bias", (W.shape[0],))))
+            n_in = W.shape[0]
+        self.action_dim = n_in
+        if self.action_dim > _lib.MPPI_MAX_ADIM:
+            raise ValueError(f"the last layer has {self.action_dim} outputs; an action has at most {_lib.MPPI_MAX_ADIM}")
+        self.activation = activation
+        self.obs_shift = _f32(obs_shift, "obs_shift", (_lib.NOBS,))
+        self.obs_scale = _f32(obs_scale, "obs_scale", (_lib.NOBS,))
+        self.log_std = _f32(log_std, "log_std", (self.action_dim,))
+        self.low = _f32(low, "low", (self.action_dim,))
+        self.high = _f32(high, "high", (self.action_dim,))
+        self.seed = int(seed)
+        self._dev = None
+        self._env = None
+
+    @classmethod
+    def from_torch(cls, net, **kw) -> "MlpPolicy":
+        """From a torch.nn.Sequential of Linear layers with Tanh or ReLU modules (all the same) between them."""
+        import torch.nn as nn
+
+        mods = list(net)
+        if not mods or len(mods) % 2 == 0:
+            raise ValueError("from_torch needs Linear layers with one activation module between each pair")
+        lin, acts = mods[0::2], mods[1::2]
+        if not all(isinstance(m, nn.Linear) for m in lin):
+            raise ValueError("from_torch: every other module, from the first, must be a torch.nn.Linear")
+        kinds = {type(m) for m in acts}
+        if not kinds <= {nn.Tanh, nn.ReLU} or len(kinds) > 1:
+            raise ValueError("from_torch: the modules between the Linear layers must be all Tanh or all ReLU")
+        activation = "relu" if kinds == {nn.ReLU} else "tanh"
+        return cls([(m.weight, m.bias) for m in lin], activation=activation, **kw)
+
+    # ------------------------------------------------------------------ the device object
+    def bind(self, env) -> "MlpPolicy":
+        """Create the device object on the env's device (a PickPlaceVecEnv whose action dimension is the last
+        layer's width); a policy bound before is closed first."""
+        if env.action_dim != self.action_dim:
+            raise ValueError(f"the policy's last layer has {self.action_dim} outputs, the env's action_dim is {env.action_dim}")
+        self.close()
+        low, high = self.low, self.high
+        if low is None or high is None:
+            from .planner import action_box
+
+            box_low, box_high = action_box(env._action_mode)
+            low = np.asarray(box_low, np.float32) if low is None else low
+            high = np.asarray(box_high, np.float32) if high is None else high
+        self._dev = _lib.Policy(env.sim, self.layers, ACTIVATIONS.index(self.activation), self.obs_shift, self.obs_scale,
+                                self.log_std, low, high, self.seed)
+        self._env = env
+        self.bound_low, self.bound_high = low, high
+        return self
+
+    @property
+    def device_policy(self) -> "_lib.Policy":
+        if self._dev is None:
+            raise RuntimeError("the policy is not bound: call bind(env) first")
+        return self._dev
+
+    def eval(self, obs):
+        """The network alone: mean [n, A] (a CUDA tensor) of observations [n, 85], no noise, no clamp."""
+        import torch
+
+        dev, env = self.device_policy, self._env
+        x = torch.as_tensor(obs, dtype=torch.float32, device=env.device)
+        if x.dim() != 2 or x.shape[1] != _lib.NOBS:
+            raise ValueError(f"obs must be [n, {_lib.NOBS}], got {tuple(x.shape)}")
+        x = x.contiguous()
+        out = torch.empty((x.shape[0], self.action_dim), dtype=torch.float32, device=env.device)
+        if x.shape[0]:
+            with env.sim._on_sim_stream(env.device) as (cur, sst):
+                x.record_stream(sst)
+                out.record_stream(sst)
+                dev.eval(x.data_ptr(), x.shape[0], out.data_ptr())
+        return out
+
+    def close(self):
+        if self._dev is not None:
+            self._dev.close()
+        self._dev = self._env = None

@@ -196,6 +196,43 @@ class PickPlaceVecEnv:
             self._last_action = a
         return out
 
+    def rollout_policy(self, policy, n_steps: int, record=("obs", "reward", "done"), call: int = 0) -> dict:
+        """n_steps closed-loop env steps under an MlpPolicy bound to this env (policy.MlpPolicy.bind), in the
+        fused launches of rollout(): every env's wave evaluates the network on the observation the env holds
+        (after an autoreset: the new episode's first) between two env steps.  Returns {name: tensor [T, N, ...]}
+        for the names in `record`: the _lib.TRAJ_FIELDS entries as rollout() records them, always "actions"
+        [T, N, action_dim] (what the envs were stepped with; rollout(actions=...) from the same state replays the
+        call bit for bit), and on request "mean" (the network's output) and "noise" (the normal draws; increment
+        `call` per call for fresh ones)."""
+        names = (record,) if isinstance(record, str) else tuple(record or ())
+        own = ("actions", "mean", "noise")
+        for name in names:
+            if name not in _lib.TRAJ_FIELDS and name not in own:
+                raise ValueError(f"record entries must be among {tuple(_lib.TRAJ_FIELDS) + own}, got '{name}'")
+        if n_steps is None or int(n_steps) < 0:
+            raise ValueError("rollout_policy needs n_steps >= 0")
+        dev = policy.device_policy
+        if policy.action_dim != self.action_dim or policy._env is not self:
+            raise ValueError("the policy must be bound to this env (MlpPolicy.bind(env))")
+        T = int(n_steps)
+        out, rec, prec = {}, _lib.MMXTrajectory(), _lib.MMXPolicyRecord()
+        for name in names:
+            if name in own:
+                continue
+            width, dtype = _lib.TRAJ_FIELDS[name]
+            shape = (T, self.num_envs, width) if width > 1 else (T, self.num_envs)
+            out[name] = torch.empty(shape, dtype=getattr(torch, dtype), device=self.device)
+            setattr(rec, name, out[name].data_ptr())
+        for name in own:
+            if name == "actions" or name in names:
+                out[name] = torch.empty((T, self.num_envs, self.action_dim), dtype=torch.float32, device=self.device)
+                setattr(prec, name, out[name].data_ptr())
+        if T == 0:
+            return out
+        dev.rollout(self.sim, T, call, prec, rec)
+        self._last_action = out["actions"]
+        return out
+
     # ------------------------------------------------------------------ snapshot / restore
     def snapshot(self) -> Snapshot:
         """The state of every env, on the device (mmx_snapshot; asynchronous): everything a step reads and

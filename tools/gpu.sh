@@ -26,6 +26,9 @@
 #   snapshot         snapshot / restore timing beside one step launch and the host state round trip
 #                    (tools/snapshot_time.py); SNAP_OUT = a file for the full result (default
 #                    profiles/r10_snapshot.json)
+#   policy           closed-loop policy rollout timing (tools/policy_time.py): the obs -> torch MLP -> step loop,
+#                    rollout_policy, and the replay of its recorded actions; BASELINE_LIB = a library of the
+#                    baseline commit for the loop; POLICY_OUT = a file for the full result
 # Env: R (round tag, default r06), MMX_LIB_PATH (a library other than the product for every recipe).
 set -o pipefail
 cd ${GRAFT_REPO_ROOT:-$(pwd)}; ROOT=$(pwd); mkdir -p gpurun_out
@@ -131,6 +134,10 @@ traj() {
   timeout -k 10 400 python -u tools/traj_time.py ${BASELINE_LIB:+--baseline-lib $BASELINE_LIB} ${TRAJ_OUT:+--out $TRAJ_OUT}
 }
 
+policy() {
+  timeout -k 10 500 python -u tools/policy_time.py ${BASELINE_LIB:+--baseline-lib $BASELINE_LIB} ${POLICY_OUT:+--out $POLICY_OUT}
+}
+
 occupancy() {
   mkdir -p gpurun_out/occ
   local a="--steps 128 --warmup 32 --repeats 3 --no-cpu-baseline"
@@ -155,6 +162,7 @@ for recipe in "$@"; do
     ab) bash tools/ab.sh ;;
     occupancy) occupancy ;;
     traj) traj ;;
+    policy) policy ;;
     snapshot) timeout -k 10 300 python -u tools/snapshot_time.py ${SNAP_OUT:+--out $SNAP_OUT} ;;
     *) echo "unknown recipe $recipe"; false ;;
   esac || exit $?

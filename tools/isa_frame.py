@@ -11,7 +11,9 @@ import sys
 
 FUNCS = ("_Z7substepifPf", "mmx_env_step_kernel", "mmx_env_step_budget_kernel", "mmx_env_step_kernel_l192",
          "_Z10step_beginRK8MMXStateiPKfii",
-         "_Z11step_finishRK8MMXStatei")  # (a listing holds one of the two kernels: the other is left out)
+         "_Z11step_finishRK8MMXStatei", "mmx_env_traj_kernel", "mmx_env_traj_kernel_l192",
+         "_Z10policy_actRK8MMXStateRK9MmxPolicyRK12MMXPolicyRecij", "mmx_env_policy_kernel",
+         "mmx_env_policy_kernel_l192")  # (a listing holds one layout's kernels: the other's are left out)
 
 # a function's label: `name:` in a -S listing, `0000000000001900 <name>:` in llvm-objdump -d output
 LABEL = re.compile(r"^(?:[0-9a-f]+ <)?([A-Za-z_][\w.$]*)>?:\s*(;.*)?$")
@@ -44,8 +46,10 @@ def frames(path):
     out = {}
     for f in FUNCS:
         seg = re.search(rf"\.set (?:\.L)?{re.escape(f)}\.private_seg_size, (\d+)(\+max)?", txt)
+        if not seg and f.startswith("_Z10policy_act"):
+            continue  # (a listing of before the policy kernel)
         vg = re.search(rf"\.set (?:\.L)?{re.escape(f)}\.num_vgpr, (?:max\()?(\d+)", txt)
-        if f.startswith("mmx_env_step_") and not seg:
+        if f.startswith("mmx_env_") and not seg:
             continue
         out[f] = {"private_seg_bytes_per_lane": int(seg.group(1)) if seg else None,
                   "plus_callees": bool(seg and seg.group(2)), "vgpr": int(vg.group(1)) if vg else None, **ops[f]}
