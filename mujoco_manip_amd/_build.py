@@ -67,12 +67,12 @@ TEST_VARIANTS = {
     # list-vs-full-prune bit-identity test)
     "libmmx_nolist.so": ["MMX_CAND_CAP=1"],
     # the 192-row kernel with one of its two waves held back after barriers C and A (MMX_HELPER_DELAY in
-    # mmx_step.inc: 1 the helper wave, 2 the env wave), and probe set 14 (full prunes and the list's
+    # mmx_step_lds.inc: 1 the helper wave, 2 the env wave), and probe set 14 (full prunes and the list's
     # displacement bound in the stats): results may not depend on which wave is late
     "libmmx_hdelay.so": ["MMX_HELPER_DELAY=1", "MMX_PROBE=14"],
     "libmmx_edelay.so": ["MMX_HELPER_DELAY=2", "MMX_PROBE=14"],
     # the budgeted step launches' clock replaced by a cost of 1 + env % 3 "ticks" per env step (MMX_BUDGET_SYNTH in
-    # mmx_step.inc): envs progress unevenly in the same way on every machine (tests/test_step_budget.py)
+    # mmx_step_kernels.inc): envs progress unevenly in the same way on every machine (tests/test_step_budget.py)
     "libmmx_synth.so": ["MMX_BUDGET_SYNTH=1"],
 }
 
@@ -82,7 +82,7 @@ def lib_path(profile: bool = False) -> str:
 
 
 def _stale(lib: str) -> bool:
-    """Any source-like file of csrc/ (sources, headers, the included step file) or public header newer than `lib`."""
+    """Any source-like file of csrc/ (sources, headers, the included step file and its parts) or public header newer than `lib`."""
     if not os.path.exists(lib):
         return True
     t = os.path.getmtime(lib)

@@ -117,16 +117,18 @@ struct mmx_policy {
 namespace {
 
 // Makes the sim's device current for the duration of an entry point (NULL-stream launches and
-// hipMemcpy go to the current device) and restores the caller's device afterwards.
+// hipMemcpy go to the current device) and restores the caller's device afterwards.  From the device number
+// alone for the planner's and the policy's destroy, which may outlive their sim (a device < 0, as for no sim: no switch).
 struct DeviceGuard {
   int prev = -1;
-  explicit DeviceGuard(const mmx_sim* sim) {
-    if (sim && hipGetDevice(&prev) == hipSuccess && prev != sim->cfg.device) {
-      if (hipSetDevice(sim->cfg.device) != hipSuccess) prev = -1;
+  explicit DeviceGuard(int device) {
+    if (device >= 0 && hipGetDevice(&prev) == hipSuccess && prev != device) {
+      if (hipSetDevice(device) != hipSuccess) prev = -1;
     } else {
       prev = -1;
     }
   }
+  explicit DeviceGuard(const mmx_sim* sim) : DeviceGuard(sim ? sim->cfg.device : -1) {}
   ~DeviceGuard() {
     if (prev >= 0) (void)hipSetDevice(prev);
   }
@@ -656,12 +658,17 @@ int mmx_rollout_expert(mmx_sim* sim, int32_t n_env_steps) {
                  });
 }
 
+// the caller's record as the kernels take it (no record: every array null, nothing is written)
+static MMXTraj traj_arg(const mmx_trajectory* rec) {
+  if (!rec) return MMXTraj{};
+  return MMXTraj{rec->obs, rec->reward, rec->done, rec->reward_components, rec->target, rec->episode_i, rec->qpos, rec->qvel};
+}
+
 // The same rollout on the trajectory kernel: every launch also gets the rollout step k0 its lane has
 // reached, which selects its action rows (expert = 0) and its slices of the record `rec`.
 static int rollout_traj(mmx_sim* sim, const float* actions, int adim, int expert, int n, const mmx_trajectory* rec,
                         const char* what) {
-  MMXTraj R{};
-  if (rec) R = MMXTraj{rec->obs, rec->reward, rec->done, rec->reward_components, rec->target, rec->episode_i, rec->qpos, rec->qvel};
+  const MMXTraj R = traj_arg(rec);
   const auto traj = step_launchers(sim).traj;
   return rollout(sim, n, what, false,
                  [&](const MMXState* S, int base, int count, int ns, int k0, hipStream_t st, const int* ord, const MMXBudget*) {
@@ -943,10 +950,8 @@ int mmx_mppi_create(mmx_sim* sim, const mmx_mppi_config* c, mmx_mppi** out) {
 
 void mmx_mppi_destroy(mmx_mppi* p) {
   if (!p) return;
-  int prev = -1;
-  const bool sw = hipGetDevice(&prev) == hipSuccess && prev != p->device && hipSetDevice(p->device) == hipSuccess;
+  DeviceGuard guard(p->device);
   for (void* d : p->allocs) (void)hipFree(d);
-  if (sw) (void)hipSetDevice(prev);
   delete p;
 }
 
@@ -994,7 +999,7 @@ int mmx_mppi_get_buffers(mmx_mppi* p, mmx_mppi_buffers* out) {
   return MMX_OK;
 }
 
-// MLP policies (mmx_policy.h; mmx_policy.hip, mmx_env_policy_kernel of mmx_step.inc)
+// MLP policies (mmx_policy.h; mmx_policy.hip, mmx_env_policy_kernel of mmx_step_kernels.inc)
 int mmx_policy_create(mmx_sim* sim, const mmx_policy_config* c, mmx_policy** out) {
   if (out) *out = nullptr;
   if (!sim || !c || !out) return sim ? fail(sim, MMX_EINVAL, "mmx_policy_create: NULL argument") : MMX_EINVAL;
@@ -1037,10 +1042,8 @@ int mmx_policy_create(mmx_sim* sim, const mmx_policy_config* c, mmx_policy** out
 
 void mmx_policy_destroy(mmx_policy* p) {
   if (!p) return;
-  int prev = -1;
-  const bool sw = hipGetDevice(&prev) == hipSuccess && prev != p->device && hipSetDevice(p->device) == hipSuccess;
+  DeviceGuard guard(p->device);
   if (p->data) (void)hipFree(p->data);
-  if (sw) (void)hipSetDevice(prev);
   delete p;
 }
 
@@ -1058,8 +1061,7 @@ int mmx_rollout_policy(mmx_sim* sim, mmx_policy* policy, int32_t n_env_steps, ui
   if (policy->P.A != kDim[sim->S.action_mode])
     return fail(sim, MMX_EINVAL, "mmx_rollout_policy: the policy's action width is not the sim's action dimension");
   if (policy->device != sim->cfg.device) return fail(sim, MMX_EINVAL, "mmx_rollout_policy: the policy was created on another device");
-  MMXTraj R{};
-  if (rec) R = MMXTraj{rec->obs, rec->reward, rec->done, rec->reward_components, rec->target, rec->episode_i, rec->qpos, rec->qvel};
+  const MMXTraj R = traj_arg(rec);
   MmxPolicy P = policy->P;
   P.call_lo = (uint32_t)call, P.call_hi = (uint32_t)(call >> 32);
   const MMXPolicyRec PR{prec->actions, prec->mean, prec->noise};

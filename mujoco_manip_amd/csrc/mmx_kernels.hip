@@ -246,7 +246,7 @@ extern "C" hipError_t mmx_launch_forward(const MMXState* S, hipStream_t st) {
   return hipGetLastError();
 }
 #ifdef MMX_PHASE_CLOCK
-// the profile build's per-FSM-state sums of the 128-row step kernel (g_fsm_prof, mmx_step.inc)
+// the profile build's per-FSM-state sums of the 128-row step kernel (g_fsm_prof, mmx_step_kernels.inc)
 extern "C" hipError_t mmx_fsm_profile(double* out, int reset) {
   hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fsm_prof), sizeof(g_fsm_prof));
   if (e == hipSuccess && reset) {

@@ -1,6 +1,6 @@
 // The host seam between mmx_api.cpp and the kernel sources: every non-kernel extern "C" function that one
 // source defines and another calls, declared once.  mmx_api.cpp includes it and so does every source that
-// defines one of them (mmx_step.inc, mmx_render.hip, mmx_png.hip, mmx_snapshot.hip, mmx_mppi.hip, mmx_policy.hip), so a parameter list
+// defines one of them (mmx_step.inc, whose launchers are in mmx_step_kernels.inc, mmx_render.hip, mmx_png.hip, mmx_snapshot.hip, mmx_mppi.hip, mmx_policy.hip), so a parameter list
 // changed on one side only is a compile error.  (The diagnostic exports that tools load through ctypes,
 // mmx_fsm_profile and mmx_render_clock among them, are not called across sources and are not listed.)
 #ifndef MMX_LAUNCH_H
@@ -16,7 +16,8 @@ struct MMXPolicyRec;
 
 extern "C" {
 
-// mmx_step.inc, built once per LDS-row layout: the launchers' names carry the layout's suffix
+// mmx_step_kernels.inc (the last part of mmx_step.inc), built once per LDS-row layout: the launchers' names
+// carry the layout's suffix
 #define MMX_DECLARE_STEP_LAUNCHERS(sfx)                                                                                \
   hipError_t mmx_launch_step##sfx(const MMXState* S, const float* action, int adim, int expert, int base, int count,   \
                                   int nsteps, hipStream_t st, const int* order);                                       \

@@ -1,5 +1,5 @@
 // The closed forms of the MLP policy (mmx_policy_create / mmx_policy_eval / mmx_rollout_policy, include/mmx_api.h)
-// as host + device inline functions: mmx_env_policy_kernel (mmx_step.inc) and mmx_policy_eval_kernel
+// as host + device inline functions: mmx_env_policy_kernel (mmx_step_kernels.inc) and mmx_policy_eval_kernel
 // (mmx_policy.hip) call them, and a stand-alone host program (tests/host/mmx_policy_selftest.cpp, plain g++) runs
 // the very same code.  The packed-weight indexing, one neuron's dot product, the activation, the action formula, a
 // scalar reference of the whole forward pass, and the wave's forward pass over LDS scratch.

@@ -1,6 +1,6 @@
 // The MLP policy's network alone (mmx_policy_eval, include/mmx_api.h): observations the caller supplies ->
 // the network's output (the mean, before noise and clamp).  One wave per row: the forward pass is
-// policy_forward_wave of mmx_policy.h, the very function mmx_env_policy_kernel (mmx_step.inc) runs between two env
+// policy_forward_wave of mmx_policy.h, the very function mmx_env_policy_kernel (mmx_step_kernels.inc) runs between two env
 // steps, here on LDS of its own.
 #include <hip/hip_runtime.h>
 #include <stdint.h>

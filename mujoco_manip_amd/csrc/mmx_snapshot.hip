@@ -1,7 +1,7 @@
 // Snapshot and restore of whole environments on the device (mmx_snapshot / mmx_restore, include/mmx_api.h).
 //
 // What crosses a launch for one env is a dozen env-major arrays of MMXState (load_env / store_env and the
-// EPI / EPF accesses of mmx_step.inc, the random stream, the facade's outputs and, with cameras, the body
+// EPI / EPF accesses of mmx_step_task.inc, the random stream, the facade's outputs and, with cameras, the body
 // poses the renderer draws from).  A record is those rows of one env back to back, in the order of
 // kFields below (the order documented in mmx_api.h and mirrored by _lib.SNAPSHOT_FIELDS):
 //

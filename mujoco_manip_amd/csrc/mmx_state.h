@@ -3,8 +3,8 @@
 // Layout: env-major ("array of per-env records"): field f of env i lives at ptr[i * F + f].
 // One environment is owned by one 64-lane workgroup for the whole env step, so an env's record
 // is one contiguous, coalesced read at kernel start and one write at kernel end; everything in
-// between (16 substeps) stays in that workgroup's LDS.  Shared by mmx_step.inc (device) and
-// mmx_api.cpp (host allocation / C-ABI); no torch types anywhere.
+// between (16 substeps) stays in that workgroup's LDS.  Shared by mmx_step.inc and its parts (device;
+// load_env / store_env in mmx_step_task.inc move the record) and mmx_api.cpp (host allocation / C-ABI); no torch types anywhere.
 #ifndef MMX_STATE_H
 #define MMX_STATE_H
 #include <stdint.h>

@@ -4,7 +4,8 @@ infrastructure, independent of both implementations under test.
 The kernel stores the constraint rows of a substep in one array whose order decides which loop slice and
 which memory (LDS below MMX_LDSEFC = 128 or 192 rows, the env's HBM overflow block above) a row is read
 from.  `row_layout` restates that order from the kernel's documentation (the comment above
-make_constraints_wave and the block-pair table kTB0 / kTB1 in mmx_step.inc), not from its code:
+make_constraints_wave in mmx_step_constraints.inc and the block-pair table kTB0 / kTB1 in mmx_step_lds.inc),
+not from its code:
 
 * the single rows first: the finger equality, then one row per joint past its range, padded with zero rows
   to a multiple of 4 (`nsingle`: 4, or 8 from four active limits on);

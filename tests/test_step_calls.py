@@ -1,5 +1,5 @@
 """What the env-step kernel carries across its out-of-line calls (step_begin, 16 x substep, step_finish).
-Those functions are compiled without callee-saved registers (mmx_step.inc, MMX_NO_TAIL_MARK), so the
+Those functions are compiled without callee-saved registers (mmx_step_kernels.inc, MMX_NO_TAIL_MARK), so the
 kernel itself keeps its live values over every call: the env index read from the dispatch order, the step
 and substep counters, and the contact destination handed to the last substep only.  A value lost over a
 call shows as another env's record, a substep too many or too few, or a contact record that is missing or

@@ -1,7 +1,8 @@
 """Scratch frames and spill instructions of the step kernel's functions in a hipcc -S listing: the
 evidence behind the HBM traffic of the out-of-line substep.  Usage:
     hipcc ... --cuda-device-only -S mmx_kernels.hip -o k.s ; python tools/isa_frame.py k.s [k2.s]
-(mmx_kernels.hip holds the 128-row step kernels through mmx_step.inc, mmx_step_l192.hip the 192-row ones.)
+(mmx_kernels.hip holds the 128-row step kernels through mmx_step.inc and its mmx_step_*.inc parts,
+mmx_step_l192.hip the 192-row ones.)
 Per function: private segment bytes per lane, VGPRs, scratch stores / loads (the callee-saved save
 area and spills), v_writelane / v_readlane (SGPR spills into VGPR lanes and cross-lane reads).
 functions() is the listing splitter, shared with tools/isa_same.py."""
