@@ -81,6 +81,14 @@ def lib_path(profile: bool = False) -> str:
     return LIB_PROF if profile else LIB
 
 
+def test_variant(name: str) -> str:
+    """The path of the built test library `name` (a key of TEST_VARIANTS, or libmmx_prof.so), for Sim(lib=...)."""
+    path = os.path.join(PKG, name)
+    if not os.path.exists(path):
+        raise RuntimeError("test build missing: run __graft_entry__.build()")
+    return path
+
+
 def _stale(lib: str) -> bool:
     """Any source-like file of csrc/ (sources, headers, the included step file and its parts) or public header newer than `lib`."""
     if not os.path.exists(lib):

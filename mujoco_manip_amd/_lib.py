@@ -217,36 +217,44 @@ _PROTOS = {
     "mmx_kernel_times": (C.c_int, [_vp, _fp, _i32p, _fp, _i32p]),
 }
 EXPORTED = tuple(_PROTOS)
-# exports that a library of an earlier revision lacks (tools/ab_build.py name@REV, loaded through MMX_LIB_PATH
-# as the other side of an A/B run); the product must have every one (__graft_entry__.build checks EXPORTED)
-_SINCE_BUDGET = ("mmx_set_rollout_budget", "mmx_rollout_budget", "mmx_rollout_step_counts")
-_SINCE_MPPI = ("mmx_mppi_create", "mmx_mppi_destroy", "mmx_mppi_reset", "mmx_mppi_plan", "mmx_mppi_get_buffers",
-               "mmx_mppi_reweight")
-_SINCE_POLICY = ("mmx_policy_create", "mmx_policy_destroy", "mmx_policy_eval", "mmx_rollout_policy")
 
-_lib = None
+_default = None  # the handle load() gives without a path
+_handles: dict = {}  # real path -> handle: a library is loaded and bound once
 
 
-def load(build_if_missing: bool = True):
-    """Load libmmx.so (built in-tree by _build.build)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    profile = os.environ.get("MMX_PROFILE", "0") not in ("", "0")
-    # MMX_LIB_PATH: a prebuilt variant of the same sources (diagnostic probe builds, experiments)
-    path = os.environ.get("MMX_LIB_PATH") or _build.lib_path(profile)
-    if not os.path.exists(path):
-        if not build_if_missing:
+def load(path: str | None = None, build_if_missing: bool = True):
+    """The bound handle of a build of the library, one per file.  Several may be loaded side by side (ctypes
+    loads them RTLD_LOCAL: each resolves its own calls and keeps its own statics); a Sim uses the one it was
+    created with (Sim(lib=...)).
+
+    path None: the process's default, chosen once: MMX_LIB_PATH (a prebuilt variant of the same sources or a
+    library of another revision, for every sim of the process: tools/ab.sh, tools/gpu.sh), else libmmx.so,
+    or libmmx_prof.so with MMX_PROFILE=1, built in-tree by _build.build when missing and build_if_missing.
+    The in-tree product and profile libraries must export every name of _PROTOS (__graft_entry__.build checks
+    EXPORTED); any other library is bound with the names it has, and calling one it lacks is AttributeError."""
+    global _default
+    if path is None:
+        if _default is None:
+            profile = os.environ.get("MMX_PROFILE", "0") not in ("", "0")
+            path = os.environ.get("MMX_LIB_PATH")
+            if not path:
+                path = _build.lib_path(profile)
+                if not os.path.exists(path) and build_if_missing:
+                    _build.build(profile=profile)
+            _default = load(path)
+        return _default
+    real = os.path.realpath(path)
+    if real not in _handles:
+        if not os.path.exists(real):
             raise RuntimeError(f"{os.path.basename(path)} missing at {path}; run __graft_entry__.build()")
-        _build.build(profile=profile)
-    L = C.CDLL(path)
-    for name, (restype, argtypes) in _PROTOS.items():
-        if name in _SINCE_BUDGET + _SINCE_MPPI + _SINCE_POLICY and os.environ.get("MMX_LIB_PATH") and not hasattr(L, name):
-            continue
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    _lib = L
-    return L
+        L = C.CDLL(real)
+        in_tree = real in (os.path.realpath(_build.LIB), os.path.realpath(_build.LIB_PROF))
+        for name, (restype, argtypes) in _PROTOS.items():
+            if in_tree or hasattr(L, name):
+                fn = getattr(L, name)
+                fn.restype, fn.argtypes = restype, argtypes
+        _handles[real] = L
+    return _handles[real]
 
 
 def episode_seed(root: int, index: int) -> int:
@@ -267,14 +275,33 @@ def _fptr(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
 
 
-class Sim:
-    """Owner of one mmx_sim (a batch of num_envs environments on one GPU)."""
+class _Owner:
+    """Owner of one native object: `ptr`, created through the handle `L`, destroyed once by L's function DESTROY."""
+    DESTROY = ""
+
+    def close(self):
+        if getattr(self, "ptr", None) is not None and self.ptr.value:
+            getattr(self.L, self.DESTROY)(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Sim(_Owner):
+    """Owner of one mmx_sim (a batch of num_envs environments on one GPU).  lib: the path of the build of the
+    library that runs it (None: load()'s default); sims of different builds may be alive side by side."""
+    DESTROY = "mmx_destroy"
 
     def __init__(self, num_envs: int, *, action_mode: str = "ee_pos_quat_g_rel", reward_type: str = "dense",
                  max_episode_steps: int = 500, randomize_objects: bool = False,
                  spawn_x_range=(-0.20, 0.20), spawn_y_range=(0.30, 0.45), task_pool=None, fixed_task=None,
                  image_size: int = 224, autoreset: bool = False, solver_iterations: int = 30,
-                 solver_tolerance: float = 1e-6, device: int = 0, stream: int | None = None, render_effects=()):
+                 solver_tolerance: float = 1e-6, device: int = 0, stream: int | None = None, render_effects=(),
+                 lib: str | None = None):
         effects = render_effect_flags(render_effects)
         if effects and int(image_size) <= 0:
             raise ValueError("render_effects need cameras (image_size > 0)")
@@ -286,7 +313,7 @@ class Sim:
             raise ValueError(f"image_size must be in [0, 1024] (0 = no cameras), got {image_size}")
         if int(num_envs) <= 0:
             raise ValueError(f"num_envs must be positive, got {num_envs}")
-        self.L = load()
+        self.L = load(lib)
         cfg = MMXConfig()
         self.L.mmx_config_default(C.byref(cfg))
         cfg.num_envs = int(num_envs)
@@ -326,17 +353,6 @@ class Sim:
             raise RuntimeError(self.L.mmx_last_error(self.ptr).decode())
         if rc != 0:
             raise RuntimeError(f"{what} failed ({rc}): {self.L.mmx_last_error(self.ptr).decode()}")
-
-    def close(self):
-        if getattr(self, "ptr", None) is not None and self.ptr.value:
-            self.L.mmx_destroy(self.ptr)
-            self.ptr = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ---- C-ABI calls
     def reset(self, seeds=None, task_override=None, env_mask=None):
@@ -651,9 +667,10 @@ class Sim:
         return torch.as_tensor(_DevArray(ptr, shape, dtype, self), device=f"cuda:{self.cfg.device}")
 
 
-class Mppi:
+class Mppi(_Owner):
     """Owner of one mmx_mppi bound to a camera-less planner Sim of M * samples envs (mmx_mppi_* of
     include/mmx_api.h).  Close it before the planner sim."""
+    DESTROY = "mmx_mppi_destroy"
 
     def __init__(self, sim: Sim, *, horizon: int, samples: int, sigma, low, high, temperature: float = 1.0,
                  discount: float = 1.0, noise_beta: float = 0.0, seed: int = 0):
@@ -675,17 +692,6 @@ class Mppi:
         self.M = sim.num_envs // self.K
         self.buffers = MMXMppiBuffers()
         sim._check(self.L.mmx_mppi_get_buffers(self.ptr, C.byref(self.buffers)), "mmx_mppi_get_buffers")
-
-    def close(self):
-        if getattr(self, "ptr", None) is not None and self.ptr.value:
-            self.L.mmx_mppi_destroy(self.ptr)
-            self.ptr = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self, action_ptr: int):
         """Every step of every nominal plan = the device action [M][A]; the call counter to 0 (mmx_mppi_reset)."""
@@ -714,10 +720,11 @@ class Mppi:
                 for n, (shp, t) in shapes.items()}
 
 
-class Policy:
+class Policy(_Owner):
     """Owner of one mmx_policy on the device of `sim` (mmx_policy_* of include/mmx_api.h): an MLP on the numeric
     observation.  layers: [(W [out, in], b [out] or None), ...] float32 numpy arrays; the other arrays float32 or
     None.  Close it before the sim."""
+    DESTROY = "mmx_policy_destroy"
 
     def __init__(self, sim: Sim, layers, activation: int, obs_shift=None, obs_scale=None, log_std=None, low=None,
                  high=None, seed: int = 0):
@@ -743,17 +750,6 @@ class Policy:
         if rc != 0 or not out.value:
             raise ValueError(f"mmx_policy_create failed ({rc}): {self.L.mmx_last_error(sim.ptr).decode()}")
         self.ptr = out
-
-    def close(self):
-        if getattr(self, "ptr", None) is not None and self.ptr.value:
-            self.L.mmx_policy_destroy(self.ptr)
-            self.ptr = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def eval(self, obs_ptr: int, n: int, out_ptr: int):
         """mean [n][A] at out_ptr of the observations [n][85] at obs_ptr (device pointers; mmx_policy_eval,

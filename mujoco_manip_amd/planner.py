@@ -51,7 +51,8 @@ class MppiPlanner:
                 reward_type=env._reward_type, image_size=0, max_episode_steps=int(c.max_episode_steps),
                 randomize_objects=bool(c.randomize_objects), spawn_x_range=tuple(c.spawn_x_range),
                 spawn_y_range=tuple(c.spawn_y_range), autoreset=False, device=int(c.device),
-                solver_iterations=int(c.solver_iterations), solver_tolerance=float(c.solver_tolerance))
+                solver_iterations=int(c.solver_iterations), solver_tolerance=float(c.solver_tolerance),
+                lib=env.sim.L._name)  # the controlled env's build of the library
         try:
             self.mppi = _lib.Mppi(self.sim_env.sim, horizon=self.H, samples=self.K, sigma=sigma, low=low, high=high,
                                   temperature=temperature, discount=discount, noise_beta=noise_beta, seed=seed)

@@ -14,7 +14,9 @@ types.  Differences, all documented in DESIGN.md:
     seed per env;
   * with autoreset=True an env that terminated/truncated (or whose FSM expert finished: reported
     as truncated) is reset inside the same step (the returned obs is the first obs of the new
-    episode).
+    episode);
+  * lib=<path> runs the env on that build of the library (_lib.load: a test build, a library of another
+    revision) beside envs on other builds; None is the process's default.
 """
 from __future__ import annotations
 
@@ -53,7 +55,7 @@ class PickPlaceVecEnv:
                  render_mode: str | None = None, max_episode_steps: int = MAX_EPISODE_STEPS,
                  randomize_objects: bool = False, spawn_x_range=(-0.20, 0.20), spawn_y_range=(0.30, 0.45),
                  autoreset: bool = False, device: int = 0, solver_iterations: int = 30,
-                 solver_tolerance: float = 1e-6, render_effects=()):
+                 solver_tolerance: float = 1e-6, render_effects=(), lib: str | None = None):
         if not torch.cuda.is_available():
             raise RuntimeError("PickPlaceVecEnv needs an MI355X GPU (HIP); no CPU fallback exists")
         pool = TASK_SETS[tasks] if isinstance(tasks, str) else list(tasks)
@@ -73,7 +75,7 @@ class PickPlaceVecEnv:
                             fixed_task=None if task is None else task_index(task), image_size=image_size,
                             autoreset=autoreset, solver_iterations=solver_iterations,
                             solver_tolerance=solver_tolerance, device=device, stream=stream,
-                            render_effects=render_effects)
+                            render_effects=render_effects, lib=lib)
         s = self.sim
         self.action_dim = s.action_dim
         self._obs = s.view("obs", _lib.NOBS)

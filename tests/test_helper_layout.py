@@ -6,16 +6,13 @@ count and the broadphase list's displacement bound into the stats).  Whatever on
 while the other still writes it differs between the two builds, and from the 128-row layout, which runs
 the same phases in turn on one wave.
 
-Each run is a child process (the binding loads one library per process), one after another:
+Each run is a sim of its own build in this process (PickPlaceVecEnv(lib=...)), one alive at a time:
   R128  libmmx_hdelay.so, 128 rows (no helper wave: the timing-free layout, carrying the probe only)
   H     libmmx_hdelay.so, 192 rows (the helper wave late)
   E     libmmx_edelay.so, 192 rows (the env wave late)
 64 C3 envs, 50 lockstep expert steps; after every step a SHA-256 of (a) qpos, qvel, ctrl, (b) the last
 substep's contact list, (c) the full-prune counts, (d) the displacement bounds, and the FSM states."""
-import json
-import os
-import subprocess
-import sys
+import hashlib
 
 import numpy as np
 import pytest
@@ -23,92 +20,80 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_ENVS, N_STEPS, SEED_ROOT = 64, 50, 42
 FSM_LIFT = 4
-
-CHILD_DIGEST = r"""
-import sys, hashlib
-import numpy as np
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/oracle")
-import torch
-import oracle_py as O
-from mujoco_manip_amd import _lib
-from mujoco_manip_amd.vec_env import PickPlaceVecEnv
-n, steps, rows = int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])
-env = PickPlaceVecEnv(n, tasks="all", action_mode="abs_pos", reward_type="staged", randomize_objects=True,
-                      autoreset=False, image_size=0)
-assert env.sim.step_rows == rows, env.sim.step_rows
-env.reset(seed=[O.episode_seed(42, i) for i in range(n)])
-aux0, aux1 = _lib.STAT_FIELDS.index("cyc_aux0"), _lib.STAT_FIELDS.index("cyc_aux1")
-contacts = env.sim.view("contacts", _lib.MAXCON * _lib.CON_F)
-def sha(*ts):
-    h = hashlib.sha256()
-    for t in ts:
-        h.update(t.contiguous().cpu().numpy().tobytes())
-    return h.hexdigest()[:16]
-err, lift = 0, 0
-for t in range(steps):
-    env.step(env.expert_plan(16))
-    torch.cuda.synchronize()
-    fsm = env.fsm_state.cpu().numpy()
-    err |= int(np.bitwise_or.reduce(env.env_error.cpu().numpy()))
-    lift += int((fsm == 4).sum())
-    print("STEP", t, sha(env.qpos, env.qvel, env.ctrl), sha(contacts), sha(env.stats[:, aux0]), sha(env.stats[:, aux1]),
-          sha(env.fsm_state), err)
-print("FULL_PRUNES", float(env.stats[:, aux0].sum()), "SUBSTEPS", float(env.stats[:, 3].sum()))
-print("LIFT_ENV_STEPS", lift, "ENV_ERROR_OR", err)
-"""
-
-CHILD_PARITY = r"""
-import sys, json
-import numpy as np
-sys.path.insert(0, sys.argv[1])
-import torch
-from mujoco_manip_amd.vec_env import PickPlaceVecEnv
-N = 4
-rng = np.random.default_rng(7)
-env = PickPlaceVecEnv(N, task=("obj_red", "bin_red"), action_mode="abs_pos", reward_type="dense")
-assert env.sim.step_rows == 192, env.sim.step_rows
-env.reset(seed=0)
-out = []
-for t in range(6):
-    a = np.zeros((N, env.action_dim), np.float32)
-    a[:, :3] = rng.uniform(-0.05, 0.05, (N, 3)) + [0.0, 0.45, 0.42]
-    a[:, -1] = float(t % 2)
-    obs, rew, term, trunc, info = env.step(torch.tensor(a, device="cuda"))
-    out.append({"action": a.tolist(), "state": obs["state"].reshape(N, -1).cpu().numpy().astype(float).tolist(),
-                "reward": rew.reshape(N).cpu().numpy().astype(float).tolist()})
-print("PARITY", json.dumps(out))
-"""
 
 _RUNS = {"R128": ("libmmx_hdelay.so", 128), "H": ("libmmx_hdelay.so", 192), "E": ("libmmx_edelay.so", 192)}
 _DIGESTS: dict = {}
 
 
-def _child(code, lib, rows, *args):
-    path = os.path.join(REPO, "mujoco_manip_amd", lib)
-    assert os.path.exists(path), "test build missing: run __graft_entry__.build()"
-    r = subprocess.run([sys.executable, "-c", code, REPO, *[str(a) for a in args]],
-                       env=dict(os.environ, MMX_LIB_PATH=path, MMX_STEP_ROWS=str(rows)),
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return r.stdout
+def _sha(*ts):
+    h = hashlib.sha256()
+    for t in ts:
+        h.update(t.contiguous().cpu().numpy().tobytes())
+    return h.hexdigest()[:16]
+
+
+def digest_run(lib, rows):
+    """N_STEPS lockstep expert steps of N_ENVS C3 envs on the build `lib`, `rows` layout -> {"steps": [[a, b, c, d, fsm]
+    per step], "lift": env steps spent in the lift phase, "err": every env_error bit seen, "prunes", "substeps"}."""
+    import oracle_py as O
+    from mujoco_manip_amd import _lib
+    from mujoco_manip_amd.vec_env import PickPlaceVecEnv
+
+    env = PickPlaceVecEnv(N_ENVS, tasks="all", action_mode="abs_pos", reward_type="staged", randomize_objects=True,
+                          autoreset=False, image_size=0, lib=lib)
+    env.sim.step_rows = rows
+    assert env.sim.step_rows == rows, env.sim.step_rows
+    env.reset(seed=[O.episode_seed(SEED_ROOT, i) for i in range(N_ENVS)])
+    aux0, aux1 = _lib.STAT_FIELDS.index("cyc_aux0"), _lib.STAT_FIELDS.index("cyc_aux1")
+    contacts = env.sim.view("contacts", _lib.MAXCON * _lib.CON_F)
+    steps, err, lift = [], 0, 0
+    for t in range(N_STEPS):
+        env.step(env.expert_plan(16))
+        torch.cuda.synchronize()
+        err |= int(np.bitwise_or.reduce(env.env_error.cpu().numpy()))
+        lift += int((env.fsm_state.cpu().numpy() == FSM_LIFT).sum())
+        steps.append([_sha(env.qpos, env.qvel, env.ctrl), _sha(contacts), _sha(env.stats[:, aux0]), _sha(env.stats[:, aux1]),
+                      _sha(env.fsm_state)])
+    out = {"steps": steps, "lift": lift, "err": err, "prunes": float(env.stats[:, aux0].sum()),
+           "substeps": float(env.stats[:, 3].sum())}
+    env.close()
+    return out
+
+
+def parity_run(lib, rows):
+    """test_env_step_parity_action_modes' abs_pos case on the build `lib`: per step (actions, state, reward)."""
+    from mujoco_manip_amd.vec_env import PickPlaceVecEnv
+
+    N = 4
+    rng = np.random.default_rng(7)
+    env = PickPlaceVecEnv(N, task=("obj_red", "bin_red"), action_mode="abs_pos", reward_type="dense", lib=lib)
+    env.sim.step_rows = rows
+    assert env.sim.step_rows == rows == 192, env.sim.step_rows
+    env.reset(seed=0)
+    out = []
+    for t in range(6):
+        a = np.zeros((N, env.action_dim), np.float32)
+        a[:, :3] = rng.uniform(-0.05, 0.05, (N, 3)) + [0.0, 0.45, 0.42]
+        a[:, -1] = float(t % 2)
+        obs, rew, term, trunc, info = env.step(torch.tensor(a, device="cuda"))
+        out.append((a, obs["state"].reshape(N, -1).cpu().numpy().astype(float), rew.reshape(N).cpu().numpy().astype(float)))
+    env.close()
+    return out
 
 
 def _digests():
-    """The three runs, once for the module: run -> {"steps": [[a, b, c, d, fsm] per step], "lift", "err"}."""
+    """The three runs, once for the module: run -> digest_run's result."""
     if not torch.cuda.is_available():
         pytest.skip("needs an MI355X")
+    from mujoco_manip_amd import _build
+
     if not _DIGESTS:
         for name, (lib, rows) in _RUNS.items():
-            out = _child(CHILD_DIGEST, lib, rows, N_ENVS, N_STEPS, rows)
-            steps = [ln.split()[2:7] for ln in out.splitlines() if ln.startswith("STEP")]
-            tail = [ln for ln in out.splitlines() if ln.startswith("LIFT_ENV_STEPS")][0].split()
-            prunes = [ln for ln in out.splitlines() if ln.startswith("FULL_PRUNES")][0]
-            assert len(steps) == N_STEPS
-            _DIGESTS[name] = {"steps": steps, "lift": int(tail[1]), "err": int(tail[3])}
-            print(name, prunes, " ".join(tail))
+            _DIGESTS[name] = d = digest_run(_build.test_variant(lib), rows)
+            assert len(d["steps"]) == N_STEPS
+            print(name, "FULL_PRUNES", d["prunes"], "SUBSTEPS", d["substeps"], "LIFT_ENV_STEPS", d["lift"], "ENV_ERROR_OR", d["err"])
     return _DIGESTS
 
 
@@ -154,7 +139,7 @@ _ORACLE_PARITY: list = []
 
 
 def _oracle_parity(actions):
-    """The fp64 oracle over the parity child's actions, once for the module: per step (state, reward)."""
+    """The fp64 oracle over the parity run's actions, once for the module: per step (state, reward)."""
     import oracle_py as O
 
     if not _ORACLE_PARITY:
@@ -176,13 +161,13 @@ def test_helper_delay_env_step_vs_oracle(run, margin):
     both runs 1.2e-6 / 9.0e-5 (CHANGELOG)."""
     if not torch.cuda.is_available():
         pytest.skip("needs an MI355X")
+    from mujoco_manip_amd import _build
+
     lib, rows = _RUNS[run]
-    out = _child(CHILD_PARITY, lib, rows)
-    steps = json.loads([ln for ln in out.splitlines() if ln.startswith("PARITY")][0][len("PARITY "):])
-    ref = _oracle_parity([np.array(s["action"], np.float32) for s in steps])
+    steps = parity_run(_build.test_variant(lib), rows)
+    ref = _oracle_parity([a for a, _, _ in steps])
     dmax, rmax = 0.0, 0.0
-    for s, (ro, rr) in zip(steps, ref):
-        got, rew = np.array(s["state"]), np.array(s["reward"])
+    for (_, got, rew), (ro, rr) in zip(steps, ref):
         dmax = max(dmax, float(np.abs(got[:, :11] - ro).max()))
         rmax = max(rmax, float(np.abs(rew - rr).max()))
         margin("max_abs_dstate", dmax, 1e-4)

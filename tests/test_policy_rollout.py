@@ -27,8 +27,6 @@ mean 0.004 %, tanh 0.31 ACT_EPS, the noise 2.7e-7 from the restatement (bound 1e
 import hashlib
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -40,7 +38,6 @@ import test_traj_rollout as TR
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-REPO = TR.REPO
 N_ENVS, N_STEPS, REL = TR.N_ENVS, TR.N_STEPS, TR.REL
 MARGINS: dict = {}  # name -> the worst fraction of its bound seen in this session
 
@@ -86,9 +83,10 @@ def make_policy(spec):
 _RUNS: dict = {}
 
 
-def policy_run(rows, mode, stochastic=False, image_size=0, call=0):
-    """rollout_policy with everything recorded -> dict(rec, final, obs0, spec, facts); cached."""
-    key = (rows, mode, stochastic, image_size, call)
+def policy_run(rows, mode, stochastic=False, image_size=0, call=0, lib=None):
+    """rollout_policy with everything recorded, on the build `lib` of the library (a path; None: the product)
+    -> dict(rec, final, obs0, spec, facts); cached."""
+    key = (rows, mode, stochastic, image_size, call, lib)
     if key in _RUNS:
         return _RUNS[key]
     A = TR.MODES[mode] if mode == "abs_pos" else 10
@@ -96,7 +94,7 @@ def policy_run(rows, mode, stochastic=False, image_size=0, call=0):
     # (spread and gain chosen on the envs' own observations: 15 % and 11 % of the outputs leave the two boxes)
     spec = make_spec(A, low=low, high=high, log_std=np.full(A, np.log(0.05), np.float32) if stochastic else None,
                      spread=1.4, obs_gain=4.0)
-    env = TR.make_env(mode=mode, rows=rows, image_size=image_size)
+    env = TR.make_env(mode=mode, rows=rows, image_size=image_size, lib=lib)
     obs0 = env._obs.cpu().numpy().copy()
     policy = make_policy(spec).bind(env)
     facts = {"lanes": env.sim.rollout_lanes, "launches": env.sim.rollout_launches(N_STEPS),
@@ -273,22 +271,7 @@ def test_tanh_sweep():
 
 
 # ------------------------------------------------------------------ 5. noise
-CHILD = r"""
-import sys
-sys.path[:0] = [sys.argv[1], sys.argv[1] + "/tests"]
-import test_policy_rollout as P
-print("DIGEST", P.digest(P.policy_run(int(sys.argv[2]), "abs_pos", stochastic=sys.argv[3] == "1")))
-"""
-
-
-def child_digest(rows, stochastic, **env):
-    r = subprocess.run([sys.executable, "-c", CHILD, REPO, str(rows), "1" if stochastic else "0"],
-                       env=dict(os.environ, **env), capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return [ln for ln in r.stdout.splitlines() if ln.startswith("DIGEST")][0].split()[1]
-
-
-def test_noise():
+def test_noise(monkeypatch):
     run = policy_run(128, "abs_pos", stochastic=True)
     rec, spec = run["rec"], run["spec"]
     A = 4
@@ -302,22 +285,30 @@ def test_noise():
     note("noisy_action_fraction", frac.max())
     assert frac.max() <= 1.0
     # the same (seed, call): the same bits; call + 1: every element differs
-    _RUNS.pop((128, "abs_pos", True, 0, 0))
+    key = (128, "abs_pos", True, 0, 0, None)
+    _RUNS.pop(key)
     again = policy_run(128, "abs_pos", stochastic=True)
     assert digest(again) == digest(run)
     other = policy_run(128, "abs_pos", stochastic=True, call=1)
     assert (other["rec"]["noise"] != rec["noise"]).all()
-    # one rollout lane in a child process: the draw does not depend on lanes or the launch plan
-    assert child_digest(128, True, MMX_STREAMS="1") == digest(run)
+    # one rollout lane: the draw does not depend on lanes or the launch plan
+    monkeypatch.setenv("MMX_STREAMS", "1")
+    _RUNS.pop(key)
+    one = policy_run(128, "abs_pos", stochastic=True)
+    _RUNS[key] = run  # (the cached run stays the four-lane one)
+    assert one["facts"]["lanes"] == 1 and run["facts"]["lanes"] == 4
+    assert digest(one) == digest(run)
 
 
 # ------------------------------------------------------------------ 6. wave delay
 @pytest.mark.parametrize("lib", ["libmmx_hdelay.so", "libmmx_edelay.so"])
 def test_under_wave_delay(lib):
+    from mujoco_manip_amd import _build
+
     run = policy_run(192, "abs_pos")
-    path = os.path.join(REPO, "mujoco_manip_amd", lib)
-    assert os.path.exists(path), "test build missing: run __graft_entry__.build()"
-    assert child_digest(192, False, MMX_LIB_PATH=path, MMX_STREAMS="4") == digest(run)
+    delayed = policy_run(192, "abs_pos", lib=_build.test_variant(lib))
+    assert delayed["facts"]["lanes"] == 4
+    assert digest(delayed) == digest(run)
 
 
 # ------------------------------------------------------------------ 7. arguments

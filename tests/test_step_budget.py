@@ -5,33 +5,24 @@ Every case rolls the same seeded envs out twice, with the switch (Sim.rollout_bu
 and off, and compares every env's whole snapshot record (rng, qpos, qvel, ctrl, warm start, kinematics cache,
 target, episode ints and floats, obs, reward, reward components, done) and its solver statistics bit for bit.
 All cases force the 128-row layout (small batches default to the 192-row one, which always runs fixed counts)
-except the one that checks the 192-row layout.  The synthetic-clock case runs the test build libmmx_synth.so
-(a cost of 1 + env % 3 "ticks" per env step instead of the clock) in a child process, since the binding loads
-one library per process; the others run the product in this process.
+except the one that checks the 192-row layout.  The synthetic-clock case binds its sims to the test build
+libmmx_synth.so (a cost of 1 + env % 3 "ticks" per env step instead of the clock); the others run the product.
 """
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LOG = 8  # MMX_ROLLOUT_LOG: rows of the per-launch count log (24 steps at 4 per launch: 6 or 7 launches per lane)
 
-# (runs as the child too: `python test_step_budget.py N STEPS MAX_EPISODE_STEPS` prints one JSON line)
 
-
-def _env(n, max_episode_steps=500):
+def _env(n, max_episode_steps=500, lib=None):
     from mujoco_manip_amd.vec_env import PickPlaceVecEnv
 
     # C3's settings (bench.py) on a few envs
     return PickPlaceVecEnv(n, tasks="all", action_mode="abs_pos", reward_type="staged", randomize_objects=True,
-                           image_size=0, autoreset=True, max_episode_steps=max_episode_steps)
+                           image_size=0, autoreset=True, max_episode_steps=max_episode_steps, lib=lib)
 
 
 def _record(env):
@@ -43,12 +34,13 @@ def _record(env):
     return buf.cpu().numpy().reshape(sim.num_envs, -1), env.stats.cpu().numpy().copy()
 
 
-def _expert_run(n, steps, budget, max_episode_steps=500, rows=128, log=0):
-    """One seeded rollout_expert(steps): (records, stats, step counts[, per-launch counts], episode ints)."""
+def _expert_run(n, steps, budget, max_episode_steps=500, rows=128, log=0, lib=None):
+    """One seeded rollout_expert(steps) on the build `lib` (a path; None: the product): (records, stats, step
+    counts[, per-launch counts], episode ints)."""
     import oracle_py as O
     from mujoco_manip_amd import _lib
 
-    env = _env(n, max_episode_steps)
+    env = _env(n, max_episode_steps, lib)
     env.sim.step_rows = rows
     env.sim.rollout_budget = budget
     assert env.sim.rollout_budget == budget
@@ -92,24 +84,25 @@ def two_lanes(monkeypatch):
     monkeypatch.delenv("MMX_PLAN", raising=False)
 
 
-def test_synthetic_clock_uneven_progress_bit_identical():
+def test_synthetic_clock_uneven_progress_bit_identical(two_lanes, monkeypatch):
     """libmmx_synth.so, 8 envs, 2 lanes, 4 steps per launch, 24 steps: with the budget on, envs of cost 1, 2
     and 3 ticks a step leave the mid-call launches at different counts (the log shows it), every env ends at
     24, and every record equals the fixed-count run's."""
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    lib = os.path.join(REPO, "mujoco_manip_amd", "libmmx_synth.so")
-    assert os.path.exists(lib), "test build missing: run __graft_entry__.build()"
-    env = {k: v for k, v in os.environ.items() if k not in ("MMX_ROLLOUT_BUDGET", "MMX_PLAN", "MMX_PROFILE")}
-    env.update(MMX_LIB_PATH=lib, MMX_STREAMS="2", MMX_FUSE="4", MMX_ROLLOUT_LOG=str(LOG))
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "8", "24", "500"], env=env, capture_output=True, text=True,
-                       timeout=120)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
-    print("per-launch counts, budget on:", out["log_on"])
-    assert out["equal"], out["first_difference"]
-    assert out["counts_on"] == [24] * 8
-    log = np.array(out["log_on"])
+    from mujoco_manip_amd import _build
+
+    monkeypatch.delenv("MMX_PROFILE", raising=False)
+    lib = _build.test_variant("libmmx_synth.so")
+    on = _expert_run(8, 24, True, log=LOG, lib=lib)
+    off = _expert_run(8, 24, False, log=LOG, lib=lib)
+    log = on[2][1]
+    print("per-launch counts, budget on:", log.tolist())
+    diff = ""
+    for k, name in ((0, "record"), (1, "stats"), (3, "episode_i")):  # every byte, the phase-clock columns too
+        a, b = np.ascontiguousarray(on[k]).view(np.uint8), np.ascontiguousarray(off[k]).view(np.uint8)
+        if not np.array_equal(a, b):
+            diff += f"{name}: envs {sorted(set(np.argwhere(a != b)[:, 0].tolist()))}; "
+    assert not diff, diff
+    assert on[2][0].tolist() == [24] * 8
     uneven = _uneven(log, 2)
     assert uneven, log.tolist()
     # the synthetic cost is the env's own: within a lane, a cheaper env is never behind a dearer one
@@ -121,7 +114,7 @@ def test_synthetic_clock_uneven_progress_bit_identical():
                 if cost[a] < cost[b]:
                     assert log[r, b0 + a] >= log[r, b0 + b], (l, r, log[r].tolist())
     # the fixed run makes no budgeted call: no counts
-    assert out["counts_off"] == [0] * 8
+    assert off[2][0].tolist() == [0] * 8
 
 
 def test_real_clock_bit_identical(two_lanes):
@@ -179,17 +172,3 @@ def test_switch_does_not_reach_the_other_paths(two_lanes):
     # and the 192-row layout agrees with the budgeted 128-row run
     np.testing.assert_array_equal(on[0], _expert_run(8, 24, True, rows=128)[0])
 
-
-if __name__ == "__main__":
-    sys.path.insert(0, REPO)
-    sys.path.insert(0, os.path.join(REPO, "oracle"))
-    n, steps, mes = (int(a) for a in sys.argv[1:4])
-    on = _expert_run(n, steps, True, max_episode_steps=mes, log=LOG)
-    off = _expert_run(n, steps, False, max_episode_steps=mes, log=LOG)
-    diff = ""
-    for k, name in ((0, "record"), (1, "stats"), (3, "episode_i")):
-        a, b = np.ascontiguousarray(on[k]).view(np.uint8), np.ascontiguousarray(off[k]).view(np.uint8)
-        if not np.array_equal(a, b):
-            diff += f"{name}: envs {sorted(set(np.argwhere(a != b)[:, 0].tolist()))}; "
-    print(json.dumps({"equal": not diff, "first_difference": diff, "counts_on": on[2][0].tolist(), "log_on": on[2][1].tolist(),
-                      "counts_off": off[2][0].tolist()}))

@@ -9,34 +9,29 @@ written after the wrong substep.
   fused     one rollout_expert(8): two env steps per launch, the plan made inside the kernel
   stepwise  eight expert_plan -> step calls: one env step per launch, the action read from memory
   prof      one rollout_expert(8) on libmmx_prof.so (the phase-clock build: it also keeps the per-phase
-            snapshot, the FSM state and two clocks live across the 16 substep calls), in a child process
-            because the binding loads one library per process
+            snapshot, the FSM state and two clocks live across the 16 substep calls), bound to its own sims
 each on the 128-row and the 192-row layout.  qpos, qvel, ctrl, observation, reward, done flags and the
 last substep's contact record are bit-identical across all six."""
 import hashlib
-import json
-import os
-import subprocess
-import sys
 
 import pytest
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_ENVS, N_STEPS, SEED = 48, 8, 42
 FIELDS = ("qpos", "qvel", "ctrl", "obs", "reward", "done", "contacts")
 
 
-def collect(rows: int, fused: bool) -> dict:
-    """One run on the loaded library: field -> SHA-256 of its bytes after the 8 env steps, plus the number
-    of contacts in the record ("ncon") and the envs with an error bit ("err")."""
+def collect(rows: int, fused: bool, lib=None) -> dict:
+    """One run on the build `lib` of the library (a path; None: the product): field -> SHA-256 of its bytes
+    after the 8 env steps, plus the number of contacts in the record ("ncon") and the envs with an error bit
+    ("err")."""
     from mujoco_manip_amd import _lib
     from mujoco_manip_amd.vec_env import PickPlaceVecEnv
 
     env = PickPlaceVecEnv(N_ENVS, tasks="all", action_mode="abs_pos", reward_type="staged", randomize_objects=True,
-                          autoreset=True, image_size=0)
+                          autoreset=True, image_size=0, lib=lib)
     env.sim.step_rows = rows
     assert env.sim.step_rows == rows
     env.reset(seed=SEED)
@@ -56,13 +51,6 @@ def collect(rows: int, fused: bool) -> dict:
     return out
 
 
-CHILD = r"""
-import sys, json
-sys.path[:0] = [sys.argv[1], sys.argv[1] + "/tests"]
-import test_step_calls as T
-print("RUNS", json.dumps({str(rows): T.collect(rows, True) for rows in (128, 192)}))
-"""
-
 _RUNS: dict = {}
 
 
@@ -70,18 +58,13 @@ def _runs():
     """The six runs, once for the module: name -> collect()'s result."""
     if not torch.cuda.is_available():
         pytest.skip("needs an MI355X")
+    from mujoco_manip_amd import _build
+
     if not _RUNS:
         for rows in (128, 192):
             _RUNS[f"fused{rows}"] = collect(rows, True)
             _RUNS[f"stepwise{rows}"] = collect(rows, False)
-        path = os.path.join(REPO, "mujoco_manip_amd", "libmmx_prof.so")
-        assert os.path.exists(path), "profile build missing: run __graft_entry__.build()"
-        r = subprocess.run([sys.executable, "-c", CHILD, REPO], env=dict(os.environ, MMX_LIB_PATH=path),
-                           capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        prof = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RUNS")][0][len("RUNS "):])
-        for rows in (128, 192):
-            _RUNS[f"prof{rows}"] = prof[str(rows)]
+            _RUNS[f"prof{rows}"] = collect(rows, True, _build.test_variant("libmmx_prof.so"))
         for name, d in _RUNS.items():
             print(name, d)
     return _RUNS

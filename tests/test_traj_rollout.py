@@ -10,9 +10,6 @@ launch plan with launches of one, two and three steps) for 11 steps with episode
 every env autoresets twice inside the window, mostly in the middle of a launch; the actions differ per
 env and per step, so a wrong step index or env index shows."""
 import hashlib
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -20,7 +17,6 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_ENVS, N_STEPS, SEED = 10, 11, 7
 REL = "ee_pos_rot6d_g_rel"
 # (action mode, action_dim passed to the library): the relative 6D mode needs 10, passed wider
@@ -46,11 +42,11 @@ def snapshot(env) -> dict:
     return out
 
 
-def make_env(n=N_ENVS, mode="abs_pos", rows=128, image_size=0, seed=SEED, max_episode_steps=4):
+def make_env(n=N_ENVS, mode="abs_pos", rows=128, image_size=0, seed=SEED, max_episode_steps=4, lib=None):
     from mujoco_manip_amd.vec_env import PickPlaceVecEnv
 
     env = PickPlaceVecEnv(n, tasks="all", action_mode=mode, reward_type="staged", randomize_objects=True,
-                          max_episode_steps=max_episode_steps, autoreset=True, image_size=image_size)
+                          max_episode_steps=max_episode_steps, autoreset=True, image_size=image_size, lib=lib)
     env.sim.step_rows = rows
     assert env.sim.step_rows == rows
     env.reset(seed=seed)
@@ -120,7 +116,7 @@ def digest(rec: dict) -> str:
 
 # ------------------------------------------------------------------ 1. given actions
 _STEPWISE: dict = {}
-_FUSED: dict = {}
+_FUSED: dict = {}  # (rows, lib) -> the abs_pos record of given_fused
 
 
 def _given_stepwise(rows, mode):
@@ -134,9 +130,10 @@ def _given_stepwise(rows, mode):
     return _STEPWISE[rows, mode]
 
 
-def given_fused(rows, mode):
-    """The fused run of the given-action case on the loaded library: (record, final buffers, launch facts)."""
-    env = make_env(mode=mode, rows=rows)
+def given_fused(rows, mode, lib=None):
+    """The fused run of the given-action case on the build `lib` (a path; None: the product): (record, final
+    buffers, launch facts)."""
+    env = make_env(mode=mode, rows=rows, lib=lib)
     acts = torch.as_tensor(make_actions(mode, N_STEPS, N_ENVS), device=env.device)
     facts = {"lanes": env.sim.rollout_lanes, "launches": env.sim.rollout_launches(N_STEPS),
              "per_launch": env.sim.rollout_steps_per_launch}
@@ -160,7 +157,7 @@ def test_given_actions_equal_stepwise(rows, mode):
     snaps, ep0 = _given_stepwise(rows, mode)
     rec, final, facts = given_fused(rows, mode)
     if mode == "abs_pos":
-        _FUSED[rows] = rec
+        _FUSED[rows, None] = rec
     # the input is worth the comparison: four staggered lanes, several launches each, multi-step launches,
     # and every env autoreset at least twice inside the window
     assert facts["lanes"] == 4
@@ -300,28 +297,18 @@ def test_cameras(overlap, expert, monkeypatch):
 
 
 # ------------------------------------------------------------------ 5. wave timing
-CHILD = r"""
-import sys, json
-sys.path[:0] = [sys.argv[1], sys.argv[1] + "/tests"]
-import test_traj_rollout as T
-print("DIGEST", T.digest(T.given_fused(192, "abs_pos")[0]))
-"""
-
-
 @pytest.mark.parametrize("lib", ["libmmx_hdelay.so", "libmmx_edelay.so"])
 def test_record_under_wave_delay(lib):
     """The 192-row kernel's record is written by the env wave with no barrier of its own, beside the
     helper wave: with either wave held back after barriers C and A of every substep (the test builds
     of tests/test_helper_layout.py) the record of the given-action case is the product library's."""
-    if 192 not in _FUSED:
-        _FUSED[192] = given_fused(192, "abs_pos")[0]
-    path = os.path.join(REPO, "mujoco_manip_amd", lib)
-    assert os.path.exists(path), "test build missing: run __graft_entry__.build()"
-    r = subprocess.run([sys.executable, "-c", CHILD, REPO], env=dict(os.environ, MMX_LIB_PATH=path, MMX_STREAMS="4"),
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    got = [ln for ln in r.stdout.splitlines() if ln.startswith("DIGEST")][0].split()[1]
-    assert got == digest(_FUSED[192])
+    from mujoco_manip_amd import _build
+
+    if (192, None) not in _FUSED:
+        _FUSED[192, None] = given_fused(192, "abs_pos")[0]
+    rec, _, facts = given_fused(192, "abs_pos", _build.test_variant(lib))
+    assert facts["lanes"] == 4
+    assert digest(rec) == digest(_FUSED[192, None])
 
 
 # ------------------------------------------------------------------ 6. refusals

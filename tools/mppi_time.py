@@ -4,8 +4,9 @@ candidates, H = 4 steps (a 4,096-env planner sim, abs_pos, staged reward, no cam
   a  the fused call: mmx_mppi_plan with the library's noise
   b  the recipe it replaces, from entry points the parent commit has: restore(snap, src), torch sampling,
      rollout_actions with reward and done recorded, torch masking, softmax and the weighted mean (no host
-     synchronisation either).  With --baseline-lib it runs on that library (e.g. the parent commit's build) in a
-     child process, because the binding loads one library per process; without, on this one
+     synchronisation either).  With --baseline-lib it runs on that library (e.g. the parent commit's build, the
+     default library of a child process through MMX_LIB_PATH, as every figure under profiles/ was measured);
+     without, on this one
   c  the rollout alone: rollout_actions, reward and done recorded, of the very candidates line a rolls out,
      from the same branched state (the branch is made before the timed call)
 

@@ -26,10 +26,10 @@ SEED = 42
 CFG = dict(tasks="all", action_mode="abs_pos", reward_type="staged", randomize_objects=True, autoreset=True, image_size=0)
 
 
-def make_env(n, seed=SEED):
+def make_env(n, seed=SEED, lib=None):
     from mujoco_manip_amd.vec_env import PickPlaceVecEnv
 
-    env = PickPlaceVecEnv(n, **CFG)
+    env = PickPlaceVecEnv(n, **CFG, lib=lib)
     env.reset(seed=[_lib.episode_seed(seed, i) for i in range(n)])
     return env
 

@@ -3,8 +3,8 @@ randomised, staged reward, no cameras), a tanh MLP 85 -> 256 -> 256 -> 4 behavio
 expert as in tools/policy_example.py (1,024 envs x 300 expert steps, 300 Adam steps, seeded), deterministic.
 
   a  the loop it replaces: obs -> torch MLP -> clamp -> Sim.step, one launch per env step, no host wait.  With
-     --baseline-lib it runs on that library (e.g. the parent commit's build) in a child process, because the
-     binding loads one library per process; without, on this one
+     --baseline-lib it runs on that library (e.g. the parent commit's build, bound to the line's sims with lib=)
+     in a child process, as every figure under profiles/ was measured; without, on this one
   b  rollout_policy with obs, reward and done recorded
   c  rollout(actions=...) replaying exactly the actions b recorded, with the same record
 
@@ -22,7 +22,6 @@ median(a) - spread(a) (exit status 1 when it fails).
   python tools/policy_time.py [--baseline-lib PATH] [--envs 4096] [--out FILE]
 """
 import argparse
-import ctypes as C
 import hashlib
 import json
 import os
@@ -35,7 +34,6 @@ import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "tools")]
-from mujoco_manip_amd import _lib  # noqa: E402
 from mujoco_manip_amd.planner import action_box  # noqa: E402
 from policy_example import SEED, cloned_policy, make_env  # noqa: E402
 
@@ -78,9 +76,10 @@ def loop_steps(env, pol, T):
         env._last_action = a  # alive until the next step is queued (same stream: ordered)
 
 
-def run_round(line, r, n, arrays, replay=None):
-    """One measurement of `line` -> ({T: seconds}, digest of the final qpos, the recorded actions (line b))."""
-    env = make_env(n)
+def run_round(line, r, n, arrays, replay=None, lib=None):
+    """One measurement of `line` on the build `lib` of the library -> ({T: seconds}, digest of the final qpos, the
+    recorded actions (line b))."""
+    env = make_env(n, lib=lib)
     mlp = None
     if line == "a":
         pol = TorchPolicy(arrays, env.device)
@@ -119,20 +118,12 @@ def run_round(line, r, n, arrays, replay=None):
 
 
 def serve(lib, arrays_file, n):
-    """Line a on a library of another commit (bound without the calls it lacks: only create / reset / step /
+    """Line a on a library of another commit (_lib.load binds the calls it has; only create / reset / step /
     synchronize are used): serves round numbers on stdin with run_round's result."""
-    L = C.CDLL(lib)
-    L.mmx_last_error.restype, L.mmx_last_error.argtypes = C.c_char_p, [C.c_void_p]
-    L.mmx_episode_seed.restype, L.mmx_episode_seed.argtypes = C.c_uint32, [C.c_uint64, C.c_int32]
-    for name, (restype, argtypes) in _lib._PROTOS.items():
-        if hasattr(L, name):
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = restype, argtypes
-    _lib._lib = L
     arrays = dict(np.load(arrays_file))
     print("ready", flush=True)
     for req in sys.stdin:
-        secs, digest, _ = run_round("a", int(req), n, arrays)
+        secs, digest, _ = run_round("a", int(req), n, arrays, lib=lib)
         print(json.dumps([secs, digest]), flush=True)
 
 

@@ -10,8 +10,8 @@ stream's completion.  Five rounds; within a round the lines run one after anothe
 them alike.  One sim is alive at a time: with every line's sim alive in one process all but one of them
 ran 40 % slow (probably their rollout lanes doubling up on the process's hardware queues), and one
 process per line was as slow and noisier.
-  a  T x Sim.step on the baseline library (--baseline-lib, e.g. the parent commit's build; in a child
-     process, because the binding loads one library per process)
+  a  T x Sim.step on the baseline library (--baseline-lib, e.g. the parent commit's build, bound to the
+     line's sims with lib=; in a child process, as every figure under profiles/ was measured)
   b  T x Sim.step on this library
   c  mmx_rollout_actions with the full record (arrays allocated outside the timing)
   d  mmx_rollout_actions without a record
@@ -21,7 +21,6 @@ process per line was as slow and noisier.
   python tools/traj_time.py [--baseline-lib PATH] [--envs 4096] [--out FILE]
 """
 import argparse
-import ctypes as C
 import hashlib
 import json
 import os
@@ -41,11 +40,11 @@ ROUNDS, ADVANCE, WARMUP, WINDOWS = 5, 120, (20, 100), (20, 100)  # per round: un
 SEED = 42
 
 
-def make_env(n):
+def make_env(n, lib=None):
     from mujoco_manip_amd.vec_env import PickPlaceVecEnv
 
     env = PickPlaceVecEnv(n, tasks="all", action_mode="abs_pos", reward_type="staged", randomize_objects=True,
-                          autoreset=True, image_size=0)
+                          autoreset=True, image_size=0, lib=lib)
     env.reset(seed=[_lib.episode_seed(SEED, i) for i in range(n)])
     return env
 
@@ -72,9 +71,9 @@ def full_record(env, T):
     return rec, arrays
 
 
-def run_round(line, r, acts, n):
-    """One measurement of `line`: ({T: seconds}, digest of the final qpos)."""
-    env = make_env(n)
+def run_round(line, r, acts, n, lib=None):
+    """One measurement of `line` on the build `lib` of the library: ({T: seconds}, digest of the final qpos)."""
+    env = make_env(n, lib)
     sim, off = env.sim, r * ADVANCE
     recs = {T: full_record(env, T) for T in set(WINDOWS)} if line in "cf" else {}
 
@@ -100,16 +99,12 @@ def run_round(line, r, acts, n):
 
 
 def serve(lib, actions_file, n):
-    """Line a on a library of another commit (bound without the calls it lacks: only create / reset / step /
+    """Line a on a library of another commit (_lib.load binds the calls it has; only create / reset / step /
     synchronize are used): serves round numbers on stdin with run_round's result."""
-    L = C.CDLL(lib)
-    L.mmx_last_error.restype, L.mmx_last_error.argtypes = C.c_char_p, [C.c_void_p]
-    L.mmx_episode_seed.restype, L.mmx_episode_seed.argtypes = C.c_uint32, [C.c_uint64, C.c_int32]
-    _lib._lib = L
     acts = torch.as_tensor(np.load(actions_file), device="cuda")
     print("ready", flush=True)
     for req in sys.stdin:
-        secs, digest = run_round("a", int(req), acts, n)
+        secs, digest = run_round("a", int(req), acts, n, lib)
         print(json.dumps([secs, digest]), flush=True)
 
 
