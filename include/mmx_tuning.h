@@ -90,6 +90,15 @@ int mmx_kernel_timing(mmx_sim* sim, int32_t enable);
 int mmx_kernel_times(mmx_sim* sim, float* step_ms, int32_t* step_launches, float* render_ms,
                      int32_t* render_launches);
 
+/* The render kernels' raster layout, read only (no sim needed): an image of side image_size is rendered
+ * on a grid of side Sg = image_size rounded up to 16, in horizontal bands of mmx_render_band_rows rows (the
+ * fewest bands whose rows fit the kernel's LDS z-buffer, balanced; 0 for a size outside 1 .. 1024), and one
+ * workgroup takes mmx_render_bands_per_workgroup consecutive bands through that one z-buffer.
+ * tests/test_render_flat_pixels.py pins the image per pixel at the sizes where this layout changes shape
+ * and asserts the layout of those sizes through these calls. */
+int mmx_render_band_rows(int image_size);
+int mmx_render_bands_per_workgroup(void);
+
 #ifdef __cplusplus
 }
 #endif

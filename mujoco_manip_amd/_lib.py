@@ -215,6 +215,8 @@ _PROTOS = {
     "mmx_rollout_steps_per_launch": (C.c_int, [_vp]),
     "mmx_kernel_timing": (C.c_int, [_vp, _i32]),
     "mmx_kernel_times": (C.c_int, [_vp, _fp, _i32p, _fp, _i32p]),
+    "mmx_render_band_rows": (C.c_int, [C.c_int]),
+    "mmx_render_bands_per_workgroup": (C.c_int, []),
 }
 EXPORTED = tuple(_PROTOS)
 

@@ -856,6 +856,12 @@ extern "C" size_t mmx_render_lds_bytes() {
          sizeof(unsigned short) * kBPW * kMaxBig + kNbig * sizeof(int) + 12 * sizeof(float) + sizeof(uint32_t) * MMR_NTRI +
          sizeof(float) * 8 * MMR_NMAT + sizeof(unsigned short) * kBPW * MMR_NTRI + sizeof(RTri) * kBigCache;
 }
+// read-only views of the raster layout (include/mmx_tuning.h): the rows of a band at an image size (of its
+// raster grid, the size rounded up to 16, as both kernels ask) and the bands a workgroup takes
+extern "C" int mmx_render_band_rows(int image_size) {
+  return image_size > 0 && image_size <= 1024 ? rend_band_rows((image_size + 15) & ~15) : 0;
+}
+extern "C" int mmx_render_bands_per_workgroup() { return kBPW; }
 
 // envs [base, base + count); with a device mask (N bytes) only the envs whose byte is set.  flags and shmap:
 // the sim's opt-in effects (mmx_set_render_effects) and shadow maps, passed by the caller with every launch

@@ -7,6 +7,11 @@ projection of the cubes, and a keypoint overlay with the reference's own keypoin
 (cameras.py:56-104).  That projection divides by the camera-frame z, which is negative in front
 of a MuJoCo camera, so its (u, v) is the image point mirrored through the centre: the overlay
 checks the rendered mask at (1 - u, 1 - v).
+
+These are shares and overlaps.  The flat image is pinned per pixel, colours included, in
+tests/test_render_flat_pixels.py: every pixel of a certainty mask against the fp64 ray caster, at the
+image sizes where the kernel's band and tile layout changes (16, 20, 128, 150, 224 px).  The kernel
+still drops a face with a vertex nearer than the near plane; no test here depends on it.
 """
 import numpy as np
 import pytest
