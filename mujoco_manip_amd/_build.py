@@ -66,6 +66,12 @@ TEST_VARIANTS = {
     # a 1-entry persistent broadphase list: every collision pass runs the full 780-pair prune (the
     # list-vs-full-prune bit-identity test)
     "libmmx_nolist.so": ["MMX_CAND_CAP=1"],
+    # the GJK pair class without its cache of separating axes (csrc/mmx_gjk_cache.h): every call runs the whole
+    # GJK from its start direction (the cache-on-equals-cache-off test, tests/test_gjk_axis_cache.py), and the
+    # product's step kernels with the same counters, probe set 15 (GJK calls, separated calls, support-query
+    # rounds, cached verdicts in the stats; no phase clock): the cache is taken, and only where it is compiled in
+    "libmmx_nocache.so": ["MMX_GJK_CACHE=0", "MMX_PROBE=15"],
+    "libmmx_gjkprobe.so": ["MMX_PROBE=15"],
     # the 192-row kernel with one of its two waves held back after barriers C and A (MMX_HELPER_DELAY in
     # mmx_step_lds.inc: 1 the helper wave, 2 the env wave), and probe set 14 (full prunes and the list's
     # displacement bound in the stats): results may not depend on which wave is late

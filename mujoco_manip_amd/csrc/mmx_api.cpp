@@ -288,6 +288,7 @@ int mmx_create(const mmx_config* cfg, mmx_sim** out) {
   S.done = dalloc<int>(sim, 3 * n);
   S.con = dalloc<float>(sim, static_cast<size_t>(MMX_MAXCON) * CON_F * n);
   S.stats = dalloc<float>(sim, STAT_N * n);
+  // (zeroed, as every dalloc: the axis cache's entries in it start empty, mmx_gjk_cache.h)
   S.efc_ovf = dalloc<float>(sim, static_cast<size_t>(MMX_OVF_F) * n);
   S.fault = dalloc<int>(sim, 1);
   sim->expert_action = dalloc<float>(sim, 4 * n);

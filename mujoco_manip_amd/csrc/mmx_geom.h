@@ -10,6 +10,7 @@
 #include "mmx_device.h"
 #include "mmx_state.h"
 #include "mmx_clock.h"
+#include "mmx_gjk_cache.h"
 
 enum { GT_PLANE = 0, GT_CYL = 5, GT_BOX = 6, GT_MESH = 7 };
 
@@ -579,15 +580,19 @@ DEV bool gjk_tet(const SVx& s0, SVx& s1, SVx& s2, SVx& s3, int& n, V3& dir) {
   n = 4;
   return true;
 }
-DEV bool gjk(const GPair& GP, SVx& s0, SVx& s1, SVx& s2, SVx& s3, int& n) {
-  V3 dir = GP.A.x - GP.B.x;
+// dir: on a "separated" return (false) the direction the last support query was made along, a separating
+// axis of the pair (the axis cache keeps it, convex_convex).  rounds: the support-query rounds (mk_sv) made.
+DEV bool gjk(const GPair& GP, SVx& s0, SVx& s1, SVx& s2, SVx& s3, int& n, V3& dir, int& rounds) {
+  dir = GP.A.x - GP.B.x;
   if (norm(dir) < 1e-9f) dir = V3{1.f, 0.f, 0.f};
   s0 = mk_sv(GP, dir);
+  rounds = 1;
   n = 1;
   dir = -s0.w;
   for (int it = 0; it < 48; it++) {
     if (norm(dir) < 1e-12f) return true;
     const SVx P = mk_sv(GP, dir);
+    rounds++;
     if (dot(P.w, dir) < 0.f) return false;
     s3 = s2;  // push P; entries beyond n are dead
     s2 = s1;
@@ -780,13 +785,102 @@ DEV bool epa(const GPair& GP, SVx* V, int nv, V3& nrm, float& depth, V3& pa, V3&
 }
 
 #define EPA_SCRATCH_FLOATS (9 * EPA_MAXV + 5 * EPA_MAXF + 3 * EPA_MAXF)
-// scr: EPA_SCRATCH_FLOATS of LDS; emits at most one contact (lane 0)
+// The env's table of separating axes (mmx_gjk_cache.h) as the wave that runs the GJK pair class holds it
+// through one collision pass: lane s < MMX_AXIS_SLOTS keeps entry s in registers, loaded from the env's
+// overflow block before the pass's first pair, and is the only lane that stores it.  tab == nullptr: the pass
+// runs without the cache (the robot-obstacle pass of the step end; the build with MMX_GJK_CACHE = 0).
+struct AxisCache {
+  float* tab = nullptr;
+  int tag = 0;
+  float x = 0.f, y = 0.f, z = 0.f;
+  unsigned busy = 0u;  // wave-uniform: the slots this pass has read a verdict from or written (gjkc_slot)
+};
+DEV void axis_cache_load(AxisCache& ac, float* tab) {
+  ac.tab = tab;
+  if ((int)(threadIdx.x & 63) < MMX_AXIS_SLOTS) {
+    const float4 e = *reinterpret_cast<const float4*>(tab + MMX_AXIS_WORDS * (int)(threadIdx.x & 63));
+    ac.tag = __float_as_int(e.x);
+    ac.x = e.y;
+    ac.y = e.z;
+    ac.z = e.w;
+  }
+}
+// probe set 15 (the profile build): per collision pass the GJK calls (AUX0), the calls that ended "separated"
+// on either path (AUX1), the support-query rounds (AUX2: the cached test is one) and the verdicts the axis
+// cache gave (AUX3); EPA runs are AUX0 - AUX1
+#define GJK_PROBE15(st, k, v)                                                          \
+  do {                                                                                 \
+    if (MMX_PROBE == 15 && (threadIdx.x & 63) == 0) (st)[k] += (float)(v);             \
+  } while (0)
+// scr: EPA_SCRATCH_FLOATS of LDS; emits at most one contact (lane 0).  ac, pair: the axis cache of the pass and
+// the pair's index.  A pair with an entry is first tested along the entry's direction, one support query on the
+// current poses: beyond the margin it is separated, and the call ends as the uncached one would (no contact,
+// no flag).  Otherwise the uncached code runs unchanged from its unchanged start direction, so a penetrating
+// pair goes through exactly the instructions it goes through without the cache; a "separated" result leaves its
+// direction, normalised, in the pair's entry (the lane that owns the slot stores it).
 template <class Sink>
-DEV void convex_convex(Sink& cs, const Geom& A, const Geom& B, float* scr) {
+DEV void convex_convex(Sink& cs, const Geom& A, const Geom& B, float* scr, AxisCache& ac, int pair) {
   const GPair GP{A, B};
+  float* st = cs.E->stats;
+  const int lane = (int)(threadIdx.x & 63);
+  GJK_PROBE15(st, STAT_T_AUX0, 1);
+  unsigned hit = 0u;
+#if MMX_GJK_CACHE
+  if (ac.tab) {  // uniform
+    hit = (unsigned)__ballot(lane < MMX_AXIS_SLOTS && ac.tag == pair + 1);
+    if (hit) {  // uniform
+      const int h = __ffs((int)hit) - 1;
+      const int tag = __builtin_amdgcn_readlane(ac.tag, h);
+      const V3 d = V3{__int_as_float(__builtin_amdgcn_readlane(__float_as_int(ac.x), h)),
+                      __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ac.y), h)),
+                      __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ac.z), h))};
+      ac.busy |= 1u << h;
+      if (gjkc_dir_ok(d.x, d.y, d.z)) {  // (uniform; the verdict tests it again: the header's function is whole)
+        const SVx P = mk_sv(GP, d);
+        GJK_PROBE15(st, STAT_T_AUX2, 1);
+        if (gjkc_separated(tag, pair, d.x, d.y, d.z, P.w.x, P.w.y, P.w.z)) {
+          GJK_PROBE15(st, STAT_T_AUX1, 1);
+          GJK_PROBE15(st, STAT_T_AUX3, 1);
+          return;
+        }
+      }
+    }
+  }
+#endif
   SVx s0, s1, s2, s3;
-  int n = 0;
-  if (!gjk(GP, s0, s1, s2, s3, n)) return;
+  int n = 0, rounds = 0;
+  V3 dir;
+  const bool pen = gjk(GP, s0, s1, s2, s3, n, dir, rounds);
+  GJK_PROBE15(st, STAT_T_AUX2, rounds);
+  GJK_PROBE15(st, STAT_T_AUX1, pen ? 0 : 1);
+#if MMX_GJK_CACHE
+  if (ac.tab) {  // uniform
+    if (!pen) {
+      const int s = gjkc_slot(hit, ac.busy, pair);
+      V3 dn = dir * (1.f / norm(dir));
+      // only directions whose bits passed the test are written (behind an opaque register copy: the build
+      // has no NaN / Inf semantics, and the compiler saw these values computed)
+      asm volatile("" : "+v"(dn.x), "+v"(dn.y), "+v"(dn.z));
+      if (s >= 0 && gjkc_dir_ok(dn.x, dn.y, dn.z)) {  // uniform
+        ac.busy |= 1u << s;
+        if (lane == s) {
+          ac.tag = pair + 1;
+          ac.x = dn.x;
+          ac.y = dn.y;
+          ac.z = dn.z;
+          *reinterpret_cast<float4*>(ac.tab + MMX_AXIS_WORDS * s) = make_float4(__int_as_float(pair + 1), dn.x, dn.y, dn.z);
+        }
+      }
+    } else if (hit) {  // a penetrating pair keeps no entry: its old axis would cost a support query per substep
+      const int h = __ffs((int)hit) - 1;
+      if (lane == h) {
+        ac.tag = 0;
+        ac.tab[MMX_AXIS_WORDS * h] = 0.f;
+      }
+    }
+  }
+#endif
+  if (!pen) return;
   SVx* V = reinterpret_cast<SVx*>(scr);
   EFace* F = reinterpret_cast<EFace*>(scr + 9 * EPA_MAXV);
   int* edges = reinterpret_cast<int*>(scr + 9 * EPA_MAXV + 5 * EPA_MAXF);

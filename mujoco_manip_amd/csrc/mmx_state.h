@@ -9,6 +9,8 @@
 #define MMX_STATE_H
 #include <stdint.h>
 
+#include "mmx_gjk_cache.h"
+
 #define MMX_NQ_ 30
 #define MMX_NV_ 27
 #define MMX_NU_ 8
@@ -31,11 +33,14 @@
 #endif
 // the env's HBM overflow block, in floats: J rows [OVFEFC][16], then D, NC [OVFEFC], then the general
 // Cholesky's 27 x 27 transpose (+3: 16-byte aligned blocks), then the overflow rows' headers (bytes)
-// and the broadphase list (16-bit pair indices)
+// and the broadphase list (16-bit pair indices), then the GJK pair class's table of separating axes
+// (mmx_gjk_cache.h: MMX_AXIS_SLOTS entries of 16 bytes, 16-byte aligned; zero = empty, as mmx_create's
+// allocation leaves it)
 #define MMX_OVF_ARROW_AT(efc) (18 * (MMX_MAXEFC - (efc)))
 #define MMX_OVF_HDR_AT(efc) (MMX_OVF_ARROW_AT(efc) + 27 * 27 + 3)
 #define MMX_OVF_CAND_AT(efc) (MMX_OVF_HDR_AT(efc) + (MMX_MAXEFC - (efc) + 3) / 4)
-#define MMX_OVF_F_AT(efc) ((MMX_OVF_CAND_AT(efc) + (MMX_CAND_CAP + 1) / 2 + 3) / 4 * 4)  // (16-byte env blocks)
+#define MMX_OVF_AXIS_AT(efc) ((MMX_OVF_CAND_AT(efc) + (MMX_CAND_CAP + 1) / 2 + 3) / 4 * 4)
+#define MMX_OVF_F_AT(efc) (MMX_OVF_AXIS_AT(efc) + MMX_AXIS_SLOTS * MMX_AXIS_WORDS)  // (16-byte env blocks)
 #define MMX_OVF_F MMX_OVF_F_AT(MMX_LDSEFC)
 #define MMX_NSUBSTEP 16
 

@@ -322,6 +322,15 @@ DEV void collide_prune(EnvSh& E, bool only_ro) {
     stats[STAT_T_AUX0] += use_list ? 0.f : 1.f;
     stats[STAT_T_AUX1] = E.cdisp;
   }
+  // probe set 16 (sizes the axis cache, mmx_gjk_cache.h): the most GJK candidates one collision pass of this env
+  // has had (a maximum: read from the env's stats, tools/gpu_probe.py gjk_dist, not from the per-phase sums), and
+  // the passes with more than 2, 4 and MMX_AXIS_SLOTS of them
+  if (MMX_PROBE == 16 && LANE == 0 && !only_ro) {
+    stats[STAT_T_AUX0] = fmaxf(stats[STAT_T_AUX0], (float)ncls[2]);
+    stats[STAT_T_AUX1] += ncls[2] > 2 ? 1.f : 0.f;
+    stats[STAT_T_AUX2] += ncls[2] > 4 ? 1.f : 0.f;
+    stats[STAT_T_AUX3] += ncls[2] > MMX_AXIS_SLOTS ? 1.f : 0.f;
+  }
   PROBE(2, stats, STAT_T_AUX2);
   PROBE(5, stats, STAT_T_AUX3);
 }
@@ -336,6 +345,12 @@ DEV void collide_pairs(EnvSh& E, bool only_ro, int which) {
   const float* gx = scr + COL_GX;
   const int* cand = reinterpret_cast<const int*>(scr + COL_CAND);
   const int n0 = E.ncls[0], n1 = E.ncls[1], n2 = E.ncls[2];
+  // the axis cache's entries, one per lane, loaded before the lane-per-pair passes so that they have arrived when
+  // the first GJK pair asks (the one-wave layout; the helper wave has only the barrier before it).  The
+  // robot-obstacle pass of the step end runs without the cache: in the two-wave layout the env wave runs its GJK
+  // pairs, and an entry is only ever touched by one lane of one wave, the one that runs the substeps' GJK class.
+  AxisCache ac;
+  if (MMX_GJK_CACHE && (which & 2) && !only_ro && n2 > 0) axis_cache_load(ac, axis_of(E));  // uniform
   if (which & 1) {
     for (int k = LANE; k < n0; k += WG) {  // plane-box / plane-convex
       int p, g1, g2;
@@ -368,7 +383,7 @@ DEV void collide_pairs(EnvSh& E, bool only_ro, int which) {
       cand_unpack(cand[n0 + n1 + k], p, g1, g2);
       const Geom A = geom_lds(gx, g1), B = geom_lds(gx, g2);
       WaveSink cs(&E, p, !only_ro, g1, g2);
-      convex_convex(cs, A, B, scr + SCR_EPA);
+      convex_convex(cs, A, B, scr + SCR_EPA, ac, p);
     }
     SYNC();
     PROBE(5, stats, STAT_T_AUX2);

@@ -253,7 +253,11 @@ DEV void mj_step_wave(int max_iter, float tol, EnvSh& E, float* con_dst) {
   //   K..A  env: writes the poses and S (the cache)   helper: nothing
   //   A..P  env: the prune (reads poses, S, qvel;     helper: the dynamics (reads the same; writes M9,
   //         its displacement bound is its own)        qfrc, qacc_s and its scratch)
-  //   P..Q  env: plane and box-box pairs              helper: the GJK / EPA pairs
+  //   P..Q  env: plane and box-box pairs              helper: the GJK / EPA pairs, and with them the axis
+  //                                                   cache (mmx_gjk_cache.h; HBM, not LDS): loaded after P,
+  //                                                   stored before Q, entry s by the helper's lane s alone
+  // The env wave never touches the axis cache: its GJK pairs are those of the step end's robot-obstacle pass
+  // (collide_wave(E, true), after the last substep's Q), which runs without it, so no barrier has to order it.
   // (tests/test_helper_layout.py holds either wave back after C and A and compares the results)
   __syncthreads();  // C: the previous substep's state is in LDS; the helper runs the IK
   DELAY_ENV();

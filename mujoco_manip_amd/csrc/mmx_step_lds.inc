@@ -207,6 +207,8 @@ DEV float* lrow_of(EnvSh& E) { return E.G; }  // the Hessian staging tile
 DEV float* arrow_of(EnvSh& E) { return E.ovf + MMX_OVF_ARROW_AT(MMX_LDSEFC); }
 // the persistent broadphase list (16-bit pair indices) in the overflow block
 DEV unsigned short* cand_of(const EnvSh& E) { return reinterpret_cast<unsigned short*>(E.ovf + MMX_OVF_CAND_AT(MMX_LDSEFC)); }
+// the GJK pair class's table of separating axes in the overflow block (mmx_gjk_cache.h; AxisCache in mmx_geom.h)
+DEV float* axis_of(const EnvSh& E) { return E.ovf + MMX_OVF_AXIS_AT(MMX_LDSEFC); }
 // Constraint row i: J in E.J[.][i] (chunk-major) and D in E.D[i] for i < MMX_LDSEFC, else in the env's HBM
 // overflow block (J rows [OVFEFC][16], then D [OVFEFC]).  For a lane-owned row i = LANE + 64 q the
 // test folds at compile time (LANE's known bits), so the unrolled loops carry no branch.

@@ -13,7 +13,9 @@
 #   trace:driver     rocprofv3 kernel trace of the driver configuration + that run's own line
 #   render_pmc       SQ counters of the render kernel (C5)
 #   fsm              per-FSM-phase cycle profile (libmmx_prof.so); PROBE_SETS="1 5 ..." adds the
-#                    sub-phase probe builds build/libmmx_prof<P>.so (tools/build_probes.py)
+#                    sub-phase probe builds build/libmmx_prof<P>.so (tools/build_probes.py; 2 the prune's stages,
+#                    15 GJK calls / separated / rounds / cached verdicts; 16, a maximum, is read by
+#                    tools/gpu_probe.py gjk instead)
 #   dataset:S        f2 dataset collection + LeRobot writer, 8192 envs x 8192 episodes, S px
 #   ab               interleaved A/B of $LIBS against the product (tools/ab.sh; ROUNDS, STEPS, PMC, TESTS)
 #   occupancy        C3 env steps/s with the envs per CU lowered by dynamic LDS per workgroup (MMX_LDS_PAD;

@@ -194,6 +194,25 @@ def nefc_dist(N=4096, steps=400):
             "efc_overflow_envs": int(((env.env_error & 2) != 0).sum()) if hasattr(env, "env_error") else -1}
 
 
+def gjk_dist(N=4096, steps=160):
+    """Probe set 16 build: the most GJK candidates any env had in one collision pass of a C3 rollout (the size of
+    the axis cache's table, csrc/mmx_gjk_cache.h), and the share of passes with more than 2, 4 and
+    MMX_AXIS_SLOTS of them."""
+    from mujoco_manip_amd.vec_env import PickPlaceVecEnv
+
+    env = PickPlaceVecEnv(N, tasks="all", action_mode="abs_pos", reward_type="staged", randomize_objects=True,
+                          autoreset=True)
+    env.reset(seed=[_lib.episode_seed(42, i) for i in range(N)])
+    env.clear_stats()
+    env.rollout_expert(steps)
+    torch.cuda.synchronize()
+    st = env.sim.view("stats", _lib.STAT_N).double().cpu().numpy()
+    sub = st[:, 3].sum()
+    return {"substeps": float(sub), "max_gjk_candidates": float(st[:, 13].max()),
+            "p999_env_max": float(np.quantile(st[:, 13], 0.999)), "frac_gt2": float(st[:, 14].sum() / sub),
+            "frac_gt4": float(st[:, 15].sum() / sub), "frac_gt_slots": float(st[:, 16].sum() / sub)}
+
+
 def digest(N=2048, steps=160):
     """Bit-identity digest of a C3 expert rollout: sha256 of qpos / qvel / obs after every 20 steps
     (A/B of two builds that must agree bit for bit)."""
@@ -219,7 +238,7 @@ if __name__ == "__main__":
     os.makedirs(os.path.join(REPO, "gpurun_out"), exist_ok=True)
     for name, fn in [("phys1", lambda: physics_parity(1)), ("phys16", lambda: physics_parity(16)),
                      ("gym", gym_parity), ("expert", expert_success), ("speed", rollout_speed),
-                     ("nefc", nefc_dist), ("fsm", fsm_profile), ("digest", digest)]:
+                     ("nefc", nefc_dist), ("gjk", gjk_dist), ("fsm", fsm_profile), ("digest", digest)]:
         if len(sys.argv) > 1 and name not in sys.argv[1:]:
             continue
         t = time.time()
