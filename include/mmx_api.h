@@ -408,6 +408,52 @@ int mmx_forward(mmx_sim* sim);
  * exists in the 128-row layout only, whatever mmx_step_rows says. */
 int mmx_expert_physics(mmx_sim* sim, int32_t n_physics_steps);
 
+/* Contact forces of every env's current state (the reference: data.contact[i], mujoco.mj_contactForce(model,
+ * data, i, out), data.efc_force and data.qacc after env.step(), valid there because step() ends with mj_forward,
+ * gym_env.py:560).  mmx_contact_forces runs that forward solve as a pass of its own: kinematics, dynamics,
+ * collision, the constraint rows and the Newton solve (cfg.solver_iterations / solver_tolerance, started from
+ * qacc_warmstart as a substep's is) on the state in the sim's buffers, without integrating, then MuJoCo's
+ * mj_contactForce / mju_decodePyramid: pyramid edge force f_e = -D e on the active edges, fn = the sum of a
+ * contact's edge forces, tangent / torsion component k = mu_k (f_k+ - f_k-).  Valid after mmx_reset, mmx_step,
+ * any rollout (the final state, the rule for images), mmx_restore and mmx_set_state.  Asynchronous on the sim's
+ * stream, ordered with steps and rollouts like any other launch.
+ * The outputs are sim-owned device arrays, allocated at the first call (MMX_ENOMEM when that fails) and valid
+ * until mmx_destroy:
+ *     contact      [N][64][13] fp32   the contacts of the current state in the record of mmx_buffers.contacts
+ *                                     (dist, pos3, normal3, mu3, dim, geom1, geom2); zero past ncon
+ *     force        [N][64][5] fp32    per contact, same index: fn; the force vector in the world frame ACTING ON
+ *                                     GEOM2'S BODY (geom1's body takes the opposite), the normal pointing from
+ *                                     geom1 to geom2; the torsional torque about the normal (0 for condim 3);
+ *                                     zero past ncon
+ *     body_wrench  [N][13][6] fp32    net contact force (3) and torque about the body frame's origin (3), world
+ *                                     frame, of the 13 moving bodies in model order: links 2..8, hand 9, fingers
+ *                                     10, 11, cubes 16, 17, 18; a body's contacts are added in index order
+ *     touch        [N][2] fp32        per finger (body 10, 11): the sum of fn over the contacts between that
+ *                                     finger's geoms and any cube (the grip force)
+ *     qacc         [N][27] fp32       the solve's acceleration (data.qacc after mj_forward)
+ *     solve        [N][6] fp32        ncon; nefc (MuJoCo's count); Newton iterations; relative residual; exit
+ *                                     (0 converged, 1 fp32 stall, 2 iteration cap); overflow flags (2: contacts
+ *                                     dropped, 4: rows dropped)
+ * No floating-point atomics and a fixed order of every sum: the same state gives the same bits on every call.
+ * Not touched: every array of mmx_buffers (qacc_warmstart included: mj_forward does not advance it; contacts,
+ * stats and episode_i stay those of the last step), the images, and the step kernels' broadphase list and axis
+ * cache (the pass works in an overflow block of its own), so a sim continues bit for bit the same whether the
+ * pass runs between its steps or not.  Forces are not in a snapshot record: they are derived, and recomputed on
+ * demand after mmx_restore.
+ * MMX_EINVAL for a NULL argument, and for mmx_get_force_buffers before the first successful
+ * mmx_contact_forces (nothing is allocated yet). */
+typedef struct {
+  int32_t num_envs;
+  float* contact;      /* [N][64][13] */
+  float* force;        /* [N][64][5] */
+  float* body_wrench;  /* [N][13][6] */
+  float* touch;        /* [N][2] */
+  float* qacc;         /* [N][27] */
+  float* solve;        /* [N][6] */
+} mmx_force_buffers;
+int mmx_contact_forces(mmx_sim* sim);
+int mmx_get_force_buffers(mmx_sim* sim, mmx_force_buffers* out);
+
 /* Reward-layer parity harness (gym_env.py:341-470, 562-573).  For every env: the object at
  * obj_dev[N][3], the EE at ee_dev[N][3], gripper ctrl ctrl7_dev[N] and this step's contacts as
  * geom-id pairs pairs_dev[N][max_pairs][2] (int32, a negative id ends the list; geom ids as in the

@@ -71,6 +71,20 @@ class MMXBuffers(C.Structure):
     ]
 
 
+class MMXForceBuffers(C.Structure):
+    """mmx_force_buffers (include/mmx_api.h): the sim-owned outputs of the contact-force pass."""
+    _fields_ = [
+        ("num_envs", C.c_int32), ("contact", C.c_void_p), ("force", C.c_void_p), ("body_wrench", C.c_void_p),
+        ("touch", C.c_void_p), ("qacc", C.c_void_p), ("solve", C.c_void_p),
+    ]
+
+
+# per-env shape of every array of mmx_force_buffers; the 13 moving bodies of body_wrench, in its order
+FORCE_F, FORCE_SOLVE_F = 5, 6
+FORCE_BODIES = (2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18)
+FORCE_SOLVE_FIELDS = ("ncon", "nefc", "iterations", "residual", "exit", "overflow")
+
+
 class MMXTrajectory(C.Structure):
     """mmx_trajectory (include/mmx_api.h): caller-owned device arrays [T][N][F], NULL = not recorded."""
     _fields_ = [
@@ -190,6 +204,8 @@ _PROTOS = {
     "mmx_physics_step": (C.c_int, [_vp, _i32, _i32]),
     "mmx_forward": (C.c_int, [_vp]),
     "mmx_expert_physics": (C.c_int, [_vp, _i32]),
+    "mmx_contact_forces": (C.c_int, [_vp]),
+    "mmx_get_force_buffers": (C.c_int, [_vp, C.POINTER(MMXForceBuffers)]),
     "mmx_eval_reward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32]),
     "mmx_set_render_effects": (C.c_int, [_vp, _i32]),
     "mmx_get_render_effects": (C.c_int, [_vp]),
@@ -633,6 +649,25 @@ class Sim(_Owner):
         self._check(self.L.mmx_eval_reward(self.ptr, C.c_void_p(obj_ptr), C.c_void_p(ee_ptr), C.c_void_p(ctrl7_ptr),
                                            C.c_void_p(pairs_ptr) if pairs_ptr else None, max_pairs),
                     "mmx_eval_reward")
+
+    def contact_forces(self):
+        """The contact-force pass on the current state of every env (mmx_contact_forces; asynchronous on the
+        sim's stream): the forward solve and mj_contactForce into the arrays of force_views()."""
+        self._check(self.L.mmx_contact_forces(self.ptr), "mmx_contact_forces")
+
+    def force_views(self) -> dict:
+        """Zero-copy torch views of the contact-force pass's outputs (mmx_force_buffers), valid until the sim
+        closes; they exist from the first contact_forces() call on."""
+        import torch
+
+        if getattr(self, "_force_buffers", None) is None:
+            b = MMXForceBuffers()
+            self._check(self.L.mmx_get_force_buffers(self.ptr, C.byref(b)), "mmx_get_force_buffers")
+            self._force_buffers = b
+        b, N, dev = self._force_buffers, self.num_envs, f"cuda:{self.cfg.device}"
+        shapes = {"contact": (N, MAXCON, CON_F), "force": (N, MAXCON, FORCE_F), "body_wrench": (N, len(FORCE_BODIES), 6),
+                  "touch": (N, 2), "qacc": (N, NV), "solve": (N, FORCE_SOLVE_F)}
+        return {n: torch.as_tensor(_DevArray(getattr(b, n), shp, "<f4", self), device=dev) for n, shp in shapes.items()}
 
     def synchronize(self):
         self._check(self.L.mmx_synchronize(self.ptr), "mmx_synchronize")

@@ -77,6 +77,9 @@ struct mmx_sim {
   // (allocated when shadows are first asked for), passed to every render launch (render() below)
   int render_effects = 0;
   unsigned short* shmap = nullptr;
+  // the contact-force pass's outputs and its own overflow block (mmx_contact_forces allocates them at its first
+  // call, one block; force.contact == nullptr: not yet)
+  MMXForce force = {};
   // per-launch kernel timing (mmx_kernel_timing): an event pair around every step / render launch
   // on the stream it runs on; pairs come from a pool reused after each read-out
   bool timing = false;
@@ -767,6 +770,43 @@ int mmx_expert_physics(mmx_sim* sim, int32_t n) {
   for (int k = 0; k < n && e == hipSuccess; k += 256)  // bounded launches (a few ms each)
     e = mmx_launch_expert_physics(&sim->S, std::min(256, n - k), sim->stream);
   return hip_check(sim, e, "mmx_expert_physics");
+}
+
+int mmx_contact_forces(mmx_sim* sim) {
+  if (!sim) return MMX_EINVAL;
+  DeviceGuard guard(sim);
+  MMXForce& F = sim->force;
+  if (!F.contact) {  // one allocation, zeroed (the pass's axis cache starts empty), carved in 16-byte steps
+    const size_t n = static_cast<size_t>(sim->S.N);
+    const size_t widths[7] = {size_t(MMX_MAXCON) * CON_F, size_t(MMX_MAXCON) * FRC_F, size_t(FRC_NBODY) * 6, 2, MMX_NV_,
+                              FRC_SOLVE_F, MMX_OVF_F};
+    size_t at[8] = {0};
+    for (int k = 0; k < 7; k++) at[k + 1] = at[k] + (widths[k] * n + 3) / 4 * 4;
+    float* base = dalloc<float>(sim, at[7]);
+    if (!base) return fail(sim, MMX_ENOMEM, "mmx_contact_forces: output arrays");
+    F.force = base + at[1];
+    F.wrench = base + at[2];
+    F.touch = base + at[3];
+    F.qacc = base + at[4];
+    F.solve = base + at[5];
+    F.ovf = base + at[6];
+    F.contact = base;
+  }
+  return hip_check(sim, mmx_launch_contact_force(&sim->S, &F, sim->stream), "mmx_contact_forces");
+}
+
+int mmx_get_force_buffers(mmx_sim* sim, mmx_force_buffers* out) {
+  if (!sim || !out) return MMX_EINVAL;
+  const MMXForce& F = sim->force;
+  if (!F.contact) return fail(sim, MMX_EINVAL, "mmx_get_force_buffers: no mmx_contact_forces call yet (nothing allocated)");
+  out->num_envs = sim->S.N;
+  out->contact = F.contact;
+  out->force = F.force;
+  out->body_wrench = F.wrench;
+  out->touch = F.touch;
+  out->qacc = F.qacc;
+  out->solve = F.solve;
+  return MMX_OK;
 }
 
 int mmx_eval_reward(mmx_sim* sim, const float* obj, const float* ee, const float* ctrl7, const int32_t* pairs,

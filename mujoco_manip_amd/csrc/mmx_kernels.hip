@@ -67,6 +67,168 @@ mmx_expert_physics_kernel(MMXState S, int n) {
   store_env(S, i, E);
 }
 
+// Contact forces of the current state (mmx_contact_forces; the reference reads them after env.step(), whose last
+// call is mj_forward, gym_env.py:560): the forward part of mj_step_wave -- kinematics, dynamics, collision, the
+// row build and the Newton solve from qacc_warmstart, no integrate_wave -- then MuJoCo's mj_contactForce /
+// mju_decodePyramid on the solve, the per-body wrenches and the fingers' grip force.  A pass of its own: it
+// reads the env record, writes only the arrays of F and works in F's overflow block, never the sim's (store_env
+// is not called: qacc_warmstart, contacts, stats and the step kernels' broadphase list and axis cache stay).
+//
+// The decode: newton_wave overwrites the rows' aref (slot 15) and D, so both are taken into registers before
+// the solve and the basis-row residuals r = J x - aref are formed again afterwards from the rows' J, which the
+// solver leaves alone.  Edge e of a basis row k >= 1 is a_e r_n + b_e r_k exactly as the solver forms it
+// (edge_coef, quad_first); its force is f_e = -D e where e < 0, else 0.  A contact's four basis rows sit in one
+// DPP quad: fn = the quad's sum of f_e, component k = mu_k (f_k+ - f_k-), no LDS traffic; the quad's first lane
+// then leaves (fn, t1, t2, torsion) in the scratch region at the row's index, where the contact's lane (lane c:
+// contact c) finds it through the same type-ordered row map make_constraints_wave laid out.
+// Every sum has a fixed order (a body's lane loops over the contacts by index) and there are no atomics.
+DEV int force_body(int l) { return l < 10 ? l + 2 : l + 6; }  // 13 moving bodies: 2..11, then the cubes 16..18
+#define FRC_CON_AT MMX_MAXEFC  // per-contact (force 3, torque 3, position 3, bodies) records behind the row forces
+#define FRC_CON_W 12
+static_assert(FRC_CON_AT + MMX_MAXCON * FRC_CON_W <= SCR_FLOATS, "the force pass's scratch exceeds the scratch region");
+extern "C" __global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(2, 2)))
+mmx_contact_force_kernel(MMXState S, MMXForce F) {
+  EnvSh& E = g_E;
+  const int i = blockIdx.x;
+  if (i >= S.N) return;
+  load_env(S, i, E);
+  if (LANE == 0) E.ovf = F.ovf + (size_t)i * MMX_OVF_F;
+  SYNC();
+  kinematics_wave(E);
+  dynamics_wave(E);
+  collide_wave(E, false);
+  store_contacts(F.contact + (size_t)i * MMX_MAXCON * CON_F, E);
+  const int ncon = E.ncon;
+  CReg own;  // the lane's contact (lane c: contact c), before the row build reuses the scratch that holds it
+#pragma unroll
+  for (int k = 0; k < CL_F; k++) own.v[k] = LANE < ncon ? crec(E, LANE)[k] : 0.f;
+  float mu[RPL];
+  make_constraints_wave(E, mu);
+  const int nefc = E.nefc, nsingle = E.nsingle;
+  float aref[RPL], dd[RPL];
+#pragma unroll
+  for (int q = 0; q < RPL; q++) {
+    const int r = LANE + WG * q;
+    aref[q] = 0.f;
+    dd[q] = 0.f;
+    if (WG * q >= nefc) continue;  // uniform: the slice holds no row
+    if (r < nefc) {
+      aref[q] = jget(E, r, 15);
+      dd[q] = dget(E, r);
+    }
+  }
+  float resid = 0.f;
+  int exit = 0;
+  const int it = newton_wave(E, S.solver_max_iter, S.solver_tol, resid, exit, mu);
+  if (LANE < 27) F.qacc[(size_t)i * 27 + LANE] = E.x[LANE];
+  // the rows' forces: per slice the quad's (fn, t1, t2, torsion), held by every lane of the quad
+  ovf_fence(nefc);
+  float cf[RPL][4];
+#pragma unroll
+  for (int q = 0; q < RPL; q++) {
+    const int r = LANE + WG * q;
+#pragma unroll
+    for (int k = 0; k < 4; k++) cf[q][k] = 0.f;
+    if (WG * q >= nefc) continue;  // uniform
+    const float rr = r < nefc ? row_dot16(E, r, E.x) - aref[q] : 0.f;
+    const float rn = quad_first(rr);
+    const EdgeCoef ec = edge_coef(r, nefc, nsingle, r < nefc ? mu[q] : 0.f);
+    const float e0 = fmaf(ec.a0, rn, ec.b0 * rr), e1 = fmaf(ec.a1, rn, ec.b1 * rr);
+    const bool contact_row = r >= nsingle;  // (single rows: the equality and the limits, no contact's force)
+    const float f0 = contact_row && e0 < 0.f ? -dd[q] * e0 : 0.f, f1 = contact_row && e1 < 0.f ? -dd[q] * e1 : 0.f;
+    const float tk = ec.b0 * (f0 - f1);  // mu_k (f_k+ - f_k-); b0 = mu_k on a basis row with edges
+    cf[q][0] = quad_sum(f0 + f1);
+    cf[q][1] = dpp_f<0x55>(tk);  // quad_perm [1,1,1,1]
+    cf[q][2] = dpp_f<0xAA>(tk);  // quad_perm [2,2,2,2]
+    cf[q][3] = dpp_f<0xFF>(tk);  // quad_perm [3,3,3,3]
+  }
+  SYNC();  // every lane has read its rows: the scratch region is free
+  float* scr = scr_of(E);
+#pragma unroll
+  for (int q = 0; q < RPL; q++) {
+    const int r = LANE + WG * q;
+    if (r < nefc && r >= nsingle && (r & 3) == 0) *reinterpret_cast<float4*>(scr + r) = make_float4(cf[q][0], cf[q][1], cf[q][2], cf[q][3]);
+  }
+  // the contact's first row, as make_constraints_wave placed it: by type, contacts of one type in lane order
+  int tc = -1, brow = MMX_MAXEFC, b1 = 0, b2 = 0;
+  if (LANE < ncon) {
+    b1 = MMX_geom_body[con_g1(own)];
+    b2 = MMX_geom_body[con_g2(own)];
+    const int k1 = body_block(b1), k2 = body_block(b2);
+    int rb0 = k1 >= 0 ? k1 : k2, rb1 = (k1 >= 0 && k2 >= 0 && k2 != k1) ? k2 : BLK_NONE;
+    if (rb1 != BLK_NONE && rb1 < rb0) {
+      const int t = rb0;
+      rb0 = rb1;
+      rb1 = t;
+    }
+    tc = row_type(rb0, rb1);
+  }
+#pragma unroll
+  for (int t = 0; t < NTYPE; t++) {
+    const unsigned long long m = __ballot(tc == t);
+    if (tc == t)
+      brow = E.tbase[t] + (t == 0 ? nsingle : 0) +
+             4 * (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+  }
+  SYNC();
+  {
+    float4 c4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (LANE < ncon && brow + 3 < nefc) c4 = *reinterpret_cast<const float4*>(scr + brow);  // (else: rows past MMX_MAXEFC)
+    const V3 n = V3{own[CL_N], own[CL_N + 1], own[CL_N + 2]};
+    const V3 t1 = contact_t1(n);
+    const V3 f = n * c4.x + t1 * c4.y + cross(n, t1) * c4.z;
+    float* o = F.force + ((size_t)i * MMX_MAXCON + LANE) * FRC_F;
+    const bool live = LANE < ncon;
+    o[0] = live ? c4.x : 0.f;
+    o[1] = live ? f.x : 0.f;
+    o[2] = live ? f.y : 0.f;
+    o[3] = live ? f.z : 0.f;
+    o[4] = live ? c4.w : 0.f;
+    float* w = scr + FRC_CON_AT + FRC_CON_W * LANE;
+    w[0] = f.x; w[1] = f.y; w[2] = f.z;
+    w[3] = n.x * c4.w; w[4] = n.y * c4.w; w[5] = n.z * c4.w;
+    w[6] = own[CL_POS]; w[7] = own[CL_POS + 1]; w[8] = own[CL_POS + 2];
+    w[9] = c4.x;
+    w[10] = __int_as_float(b1);
+    w[11] = __int_as_float(b2);
+  }
+  SYNC();
+  if (LANE < FRC_NBODY) {  // the body's lane adds its contacts' forces in index order
+    const int b = force_body(LANE);
+    const V3 x = body_x(E, b);
+    V3 fs = V3{0.f, 0.f, 0.f}, ts = fs;
+    for (int c = 0; c < ncon; c++) {
+      const float* w = scr + FRC_CON_AT + FRC_CON_W * c;
+      const int c1 = __float_as_int(w[10]), c2 = __float_as_int(w[11]);
+      if (c1 != b && c2 != b) continue;
+      const float sg = c2 == b ? 1.f : -1.f;  // the force acts on geom2's body, its opposite on geom1's
+      const V3 f = V3{w[0], w[1], w[2]} * sg;
+      fs = fs + f;
+      ts = ts + cross(V3{w[6], w[7], w[8]} - x, f) + V3{w[3], w[4], w[5]} * sg;
+    }
+    float* o = F.wrench + ((size_t)i * FRC_NBODY + LANE) * 6;
+    o[0] = fs.x; o[1] = fs.y; o[2] = fs.z;
+    o[3] = ts.x; o[4] = ts.y; o[5] = ts.z;
+  } else if (LANE < FRC_NBODY + 2) {  // the grip force: finger 10 / 11 against any cube
+    const int b = 10 + LANE - FRC_NBODY;
+    float s = 0.f;
+    for (int c = 0; c < ncon; c++) {
+      const float* w = scr + FRC_CON_AT + FRC_CON_W * c;
+      const int c1 = __float_as_int(w[10]), c2 = __float_as_int(w[11]);
+      if ((c1 == b && c2 >= MMX_BODY_OBJ_RED) || (c2 == b && c1 >= MMX_BODY_OBJ_RED)) s += w[9];
+    }
+    F.touch[2 * (size_t)i + LANE - FRC_NBODY] = s;
+  } else if (LANE == FRC_NBODY + 2) {
+    float* o = F.solve + (size_t)i * FRC_SOLVE_F;
+    o[0] = (float)ncon;
+    o[1] = (float)E.nefc_mj;
+    o[2] = (float)it;
+    o[3] = resid;
+    o[4] = (float)exit;
+    o[5] = (float)(E.flags & (SHF_CON_OVF | SHF_EFC_OVF));
+  }
+}
+
 // Reward-layer parity harness (gym_env.py:341-470, 562-573): the reward of every env at the given
 // object / EE positions and gripper command, with the step's contacts given as geom-id pairs (-1
 // ends a list; robot x obstacle pairs are classified by the same geom classes as the collision
@@ -234,6 +396,10 @@ extern "C" hipError_t mmx_launch_expert(const MMXState* S, int n, float* action,
 }
 extern "C" hipError_t mmx_launch_expert_physics(const MMXState* S, int n, hipStream_t st) {
   if (n > 0) hipLaunchKernelGGL(mmx_expert_physics_kernel, dim3(S->N), dim3(WG), 0, st, *S, n);
+  return hipGetLastError();
+}
+extern "C" hipError_t mmx_launch_contact_force(const MMXState* S, const MMXForce* F, hipStream_t st) {
+  hipLaunchKernelGGL(mmx_contact_force_kernel, dim3(S->N), dim3(WG), 0, st, *S, *F);
   return hipGetLastError();
 }
 extern "C" hipError_t mmx_launch_reward(const MMXState* S, const float* obj, const float* ee, const float* ctrl7,

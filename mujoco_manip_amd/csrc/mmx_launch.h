@@ -40,6 +40,8 @@ hipError_t mmx_launch_queue(const MMXState* S, int* slot, int* next, int n_ep, c
 hipError_t mmx_launch_reset(const MMXState* S, const unsigned char* mask, const int* task, hipStream_t st);
 hipError_t mmx_launch_expert(const MMXState* S, int n, float* action, hipStream_t st);
 hipError_t mmx_launch_expert_physics(const MMXState* S, int n, hipStream_t st);
+// the contact-force pass on the current state of every env, into the arrays of F (MMXForce, mmx_state.h)
+hipError_t mmx_launch_contact_force(const MMXState* S, const MMXForce* F, hipStream_t st);
 hipError_t mmx_launch_reward(const MMXState* S, const float* obj, const float* ee, const float* ctrl7, const int* pairs,
                              int max_pairs, hipStream_t st);
 hipError_t mmx_launch_forward(const MMXState* S, hipStream_t st);

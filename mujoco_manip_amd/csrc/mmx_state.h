@@ -165,4 +165,19 @@ struct MMXBudget {
   int nominal;              // the launch's length in the fixed plan
 };
 
+// Outputs of the contact-force pass (mmx_contact_force_kernel; mmx_force_buffers of include/mmx_api.h): sim-owned
+// device arrays, allocated at the first mmx_contact_forces call, and the pass's own overflow block (rows past the
+// LDS ones, broadphase list, axis cache: the 128-row layout's, whatever the sim's step layout is), so the pass
+// never writes the block the step kernels keep their list and axis cache in
+enum { FRC_F = 5, FRC_NBODY = 13, FRC_SOLVE_F = 6 };
+struct MMXForce {
+  float* contact;  // [N][MAXCON][CON_F]
+  float* force;    // [N][MAXCON][FRC_F] fn, world force on geom2's body (3), torsional torque about the normal
+  float* wrench;   // [N][FRC_NBODY][6] force, torque about the body frame's origin (world)
+  float* touch;    // [N][2] fingers 10, 11: sum of fn over their contacts with cubes
+  float* qacc;     // [N][27]
+  float* solve;    // [N][FRC_SOLVE_F] ncon, nefc (MuJoCo's), iterations, residual, exit, overflow flags
+  float* ovf;      // [N][MMX_OVF_F_AT(128)]
+};
+
 #endif

@@ -244,6 +244,17 @@ class PickPlaceGymEnv(_Base):
         obs, info = self._vec.restore(snap, src=0 if src is None else int(src))
         return {k: v[0].cpu().numpy() for k, v in obs.items()}, info
 
+    def contact_forces(self) -> dict:
+        """Contacts and contact forces of the current state, as numpy arrays trimmed to the ncon contacts: the
+        drop-in for a loop of mujoco.mj_contactForce over data.contact after step() (PickPlaceVecEnv.contact_forces
+        gives the keys).  The per-contact arrays contact, force and geoms have ncon rows; body_wrench [13, 6],
+        touch [2], qacc [27] and solve [6] are whole."""
+        out = {k: v[0].cpu().numpy() for k, v in self._vec.contact_forces().items()}
+        n = int(out["solve"][0])
+        for k in ("contact", "force", "geoms"):
+            out[k] = out[k][:n]
+        return out
+
     def expert_action(self, n_steps: int = ACTION_REPEAT) -> np.ndarray:
         """PickAndPlaceTask.plan(n_steps) + abs_pos action (generate_dataset.py:142-148)."""
         return self._vec.expert_plan(n_steps)[0].cpu().numpy()

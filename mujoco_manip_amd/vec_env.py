@@ -275,6 +275,30 @@ class PickPlaceVecEnv:
         self._last_src = idx
         return self._obs_dict(), {}
 
+    # ------------------------------------------------------------------ contact forces
+    def contact_forces(self) -> dict:
+        """Contacts and contact forces of every env's current state (mmx_contact_forces: the forward solve and
+        mj_contactForce as a pass of its own; what data.contact, mujoco.mj_contactForce and data.qacc give in
+        the reference after step()).  Valid after reset, step, any rollout (the final state) and restore; it
+        changes nothing a step reads.  Returns torch tensors, views of sim-owned arrays that the next call
+        overwrites (the launch is asynchronous on the env's stream, ordered like a step):
+          contact [N, 64, 13]  dist, pos3, normal3, mu3, dim, geom1, geom2; zero past ncon
+          force [N, 64, 5]     fn, the world-frame force on geom2's body (geom1's takes the opposite), the
+                               torsional torque about the normal; zero past ncon
+          body_wrench [N, 13, 6]  net contact force and torque about the body frame's origin (world) of bodies
+                               _lib.FORCE_BODIES: links 2..8, hand 9, fingers 10, 11, cubes 16, 17, 18
+          touch [N, 2]         per finger, the sum of fn over its contacts with cubes (the grip force)
+          qacc [N, 27]         the solve's acceleration
+          solve [N, 6]         _lib.FORCE_SOLVE_FIELDS: ncon, nefc, iterations, residual, exit, overflow
+          geoms [N, 64, 2]     int64 geom1, geom2 (a copy; -1 past ncon)"""
+        self.sim.contact_forces()
+        out = dict(self.sim.force_views())
+        ncon = out["solve"][:, 0].to(torch.int64)
+        live = torch.arange(_lib.MAXCON, device=self.device)[None, :] < ncon[:, None]
+        geoms = out["contact"][:, :, 11:13].to(torch.int64)
+        out["geoms"] = torch.where(live[:, :, None], geoms, torch.full_like(geoms, -1))
+        return out
+
     @property
     def step_count(self) -> torch.Tensor:
         return self._epi[:, _lib.EPI["step_count"]].clone()
