@@ -369,6 +369,44 @@ int  mmx_policy_eval(mmx_policy* p, const float* obs_dev, int32_t n, float* mean
 int  mmx_rollout_policy(mmx_sim* sim, mmx_policy* policy, int32_t n_env_steps, uint64_t call,
                         const mmx_policy_record* prec, const mmx_trajectory* rec);
 
+/* DAgger rollouts (Ross et al. 2011; no reference counterpart): mmx_rollout_policy with the FSM expert beside the
+ * learner, in the same fused launches (lanes, launch plan, dispatch order, both camera paths; with cameras the
+ * numeric observation is read and the images hold the last frame).  Per rollout step t and env i, inside the launch:
+ *   1. the learner's action a_policy = the policy's action of the observation the env holds (mean, noise, clamp: as
+ *      mmx_rollout_policy, the same draws);
+ *   2. the expert's label a_expert = what mmx_expert_plan(sim, 16, .) returns at that state.  The expert plans at
+ *      EVERY step, whoever acts: its FSM only moves when it plans, so it shadows the learner as it does in a loop
+ *      that calls mmx_expert_plan ahead of every mmx_step;
+ *   3. the gate.  bit 0 (Bernoulli): u < cfg->beta, u in [0, 1) the second uniform of the policy's draw at component
+ *      12 = Philox4x32-10 with key = the policy's seed, counter = (call low, call high, i, 4 t + 3), u = (x1 >> 8)
+ *      2^-24: the counter word no noise component uses, a function of (seed, call, t, i) alone, never of lanes or
+ *      the launch plan; beta = 0 never fires, beta = 1 always.  bit 1 (takeover; off when cfg->takeover_dist == 0):
+ *      d = a_policy - a_expert over xyz, d2 = fma(dz, dz, fma(dy, dy, dx dx)) in fp32, d2 > takeover_dist^2: the
+ *      expert intervenes when the learner strays;
+ *   4. the env is stepped with a_expert (all four components) when the gate is not 0, else with a_policy.
+ * mmx_dagger_record: caller-owned device arrays; actions is required, every other may be NULL.  obs_in[t][i] is the
+ * observation the learner was given at step t (after an autoreset: the new episode's first), which pairs with
+ * expert_action[t][i] as a training example.  rec: the per-step record of mmx_rollout_actions, may be NULL.
+ * Contract: afterwards every sim-owned buffer and every slice of rec is bit for bit what the loop
+ * mmx_expert_plan(sim, 16, lab) -> mmx_step(sim, drec->actions[t], 4) over t = 0 .. n_env_steps - 1 gives from the
+ * same starting state, and expert_action[t] is that loop's lab; autoreset on the FSM's DONE, truncation and
+ * divergence behave as in that loop.
+ * n_env_steps == 0 returns MMX_OK; MMX_EINVAL, with nothing launched, for a NULL sim, policy, cfg, drec or
+ * drec->actions, n_env_steps < 0, a sim whose action_mode is not MMX_ACTION_ABS_POS, a policy whose action width is
+ * not 4, a policy created on another device, beta outside [0, 1] or not finite, takeover_dist < 0 or not finite. */
+typedef struct { float beta; float takeover_dist; } mmx_dagger_config;
+typedef struct {            /* caller-owned device arrays: float [T][N][4], but gate int32 [T][N], obs_in [T][N][85] */
+  float* actions;           /* required: the executed actions */
+  float* expert_action;     /* the label: what mmx_expert_plan(16) returns at that state */
+  float* policy_action;     /* the learner's action (after noise and clamp) */
+  float* mean;              /* as mmx_policy_record */
+  float* noise;             /* as mmx_policy_record */
+  int32_t* gate;            /* bit 0 Bernoulli, bit 1 takeover; 0: the learner acted */
+  float* obs_in;            /* the observation the learner was given at step t (pairs with the label) */
+} mmx_dagger_record;
+int  mmx_rollout_dagger(mmx_sim* sim, mmx_policy* policy, int32_t n_env_steps, uint64_t call,
+                        const mmx_dagger_config* cfg, const mmx_dagger_record* drec, const mmx_trajectory* rec);
+
 /* Batched PNG encoder (dataset emission, generate_dataset.py:250-260: LeRobot embeds image
  * features as PNG files).  Encodes n RGB8 images (device, image i at rgb_dev + i * img_stride,
  * rows of 3 * width bytes, height <= 1024, width <= MMX_PNG_MAX_WIDTH: the encoder's row-above match

@@ -7,7 +7,8 @@ environments in lockstep by HIP kernels (libmmx.so, C-ABI in include/mmx_api.h).
 """
 from .constants import ACTION_REPEAT, ALL_TASKS, BINS, OBJECTS, TASK_SETS  # noqa: F401
 
-__all__ = ["PickPlaceVecEnv", "PickPlaceGymEnv", "Snapshot", "MppiPlanner", "MlpPolicy", "build_library", "episode_seed"]
+__all__ = ["PickPlaceVecEnv", "PickPlaceGymEnv", "Snapshot", "MppiPlanner", "MlpPolicy", "DaggerBuffer", "build_library",
+           "episode_seed"]
 
 
 def build_library(force: bool = False) -> str:
@@ -39,6 +40,10 @@ def __getattr__(name):
         from .policy import MlpPolicy
 
         return MlpPolicy
+    if name == "DaggerBuffer":
+        from .dagger import DaggerBuffer
+
+        return DaggerBuffer
     if name == "PickPlaceGymEnv":
         from .gym_env import PickPlaceGymEnv
 

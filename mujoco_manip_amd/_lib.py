@@ -133,6 +133,22 @@ class MMXPolicyRecord(C.Structure):
     _fields_ = [("actions", C.c_void_p), ("mean", C.c_void_p), ("noise", C.c_void_p)]
 
 
+class MMXDaggerConfig(C.Structure):
+    """mmx_dagger_config (include/mmx_api.h): the gate of mmx_rollout_dagger."""
+    _fields_ = [("beta", C.c_float), ("takeover_dist", C.c_float)]
+
+
+class MMXDaggerRecord(C.Structure):
+    """mmx_dagger_record (include/mmx_api.h): caller-owned device arrays; actions is required."""
+    _fields_ = [("actions", C.c_void_p), ("expert_action", C.c_void_p), ("policy_action", C.c_void_p), ("mean", C.c_void_p),
+                ("noise", C.c_void_p), ("gate", C.c_void_p), ("obs_in", C.c_void_p)]
+
+
+# per-env width and dtype of every array of a DAgger record
+DAGGER_FIELDS = {"actions": (4, "float32"), "expert_action": (4, "float32"), "policy_action": (4, "float32"),
+                 "mean": (4, "float32"), "noise": (4, "float32"), "gate": (1, "int32"), "obs_in": (NOBS, "float32")}
+
+
 # per-env width and dtype of every trajectory array
 TRAJ_FIELDS = {"obs": (NOBS, "float32"), "reward": (1, "float32"), "done": (3, "int32"),
                "reward_components": (6, "float32"), "target": (4, "float32"), "episode_i": (EPI_N, "int32"),
@@ -196,6 +212,8 @@ _PROTOS = {
     "mmx_policy_destroy": (None, [_vp]),
     "mmx_policy_eval": (C.c_int, [_vp, _vp, _i32, _vp]),
     "mmx_rollout_policy": (C.c_int, [_vp, _vp, _i32, C.c_uint64, C.POINTER(MMXPolicyRecord), C.POINTER(MMXTrajectory)]),
+    "mmx_rollout_dagger": (C.c_int, [_vp, _vp, _i32, C.c_uint64, C.POINTER(MMXDaggerConfig), C.POINTER(MMXDaggerRecord),
+                                     C.POINTER(MMXTrajectory)]),
     "mmx_png_bound": (_i64, [_i32, _i32]),
     "mmx_png_scratch": (_i64, [_i32, _i32]),
     "mmx_png_encode": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
@@ -797,3 +815,10 @@ class Policy(_Owner):
         """n_env_steps closed-loop env steps of `sim` under this policy in fused launches (mmx_rollout_policy)."""
         sim._check(self.L.mmx_rollout_policy(sim.ptr, self.ptr, int(n_env_steps), int(call) & (2**64 - 1), C.byref(prec),
                                              None if record is None else C.byref(record)), "mmx_rollout_policy")
+
+    def rollout_dagger(self, sim: Sim, n_env_steps: int, call: int, cfg: MMXDaggerConfig, drec: MMXDaggerRecord,
+                       record: MMXTrajectory | None = None):
+        """n_env_steps env steps of `sim` under this policy or the FSM expert, by the gate of cfg, with the expert's
+        label recorded at every step (mmx_rollout_dagger)."""
+        sim._check(self.L.mmx_rollout_dagger(sim.ptr, self.ptr, int(n_env_steps), int(call) & (2**64 - 1), C.byref(cfg),
+                                             C.byref(drec), None if record is None else C.byref(record)), "mmx_rollout_dagger")

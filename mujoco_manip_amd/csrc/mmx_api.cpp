@@ -16,6 +16,7 @@
 
 #include "../../include/mmx_api.h"
 #include "../../include/mmx_tuning.h"
+#include "mmx_dagger.h"
 #include "mmx_launch.h"
 #include "mmx_mppi.h"
 #include "mmx_plan.h"
@@ -448,10 +449,13 @@ struct StepLaunchers {
   decltype(&mmx_launch_traj) traj;
   decltype(&mmx_launch_physics) physics;
   decltype(&mmx_launch_policy) policy;
+  decltype(&mmx_launch_dagger) dagger;
 };
 StepLaunchers step_launchers(const mmx_sim* sim) {
-  return sim->step_rows == 192 ? StepLaunchers{mmx_launch_step_l192, mmx_launch_traj_l192, mmx_launch_physics_l192, mmx_launch_policy_l192}
-                               : StepLaunchers{mmx_launch_step, mmx_launch_traj, mmx_launch_physics, mmx_launch_policy};
+  return sim->step_rows == 192 ? StepLaunchers{mmx_launch_step_l192, mmx_launch_traj_l192, mmx_launch_physics_l192, mmx_launch_policy_l192,
+                                               mmx_launch_dagger_l192}
+                               : StepLaunchers{mmx_launch_step, mmx_launch_traj, mmx_launch_physics, mmx_launch_policy,
+                                               mmx_launch_dagger};
 }
 // floats per env that each action mode's action needs
 constexpr int kDim[5] = {4, 8, 10, 8, 10};
@@ -1110,6 +1114,34 @@ int mmx_rollout_policy(mmx_sim* sim, mmx_policy* policy, int32_t n_env_steps, ui
   return rollout(sim, n_env_steps, "mmx_rollout_policy", false,
                  [&](const MMXState* S, int base, int count, int ns, int k0, hipStream_t st, const int* ord, const MMXBudget*) {
                    return launch(S, &R, &P, &PR, base, count, ns, k0, st, ord);
+                 });
+}
+
+// DAgger rollouts (mmx_dagger.h; mmx_env_dagger_kernel of mmx_step_kernels.inc): mmx_rollout_policy's launches
+// with the FSM expert planning beside the learner and a gate choosing who acts
+int mmx_rollout_dagger(mmx_sim* sim, mmx_policy* policy, int32_t n_env_steps, uint64_t call, const mmx_dagger_config* cfg,
+                       const mmx_dagger_record* drec, const mmx_trajectory* rec) {
+  if (!sim || !policy || !cfg || !drec || !drec->actions || n_env_steps < 0)
+    return sim ? fail(sim, MMX_EINVAL, "mmx_rollout_dagger: bad arguments (NULL policy, cfg, drec or actions, or n_env_steps < 0)")
+               : MMX_EINVAL;
+  if (sim->S.action_mode != MMX_ACTION_ABS_POS) return fail(sim, MMX_EINVAL, "mmx_rollout_dagger needs action_mode abs_pos");
+  if (policy->P.A != 4) return fail(sim, MMX_EINVAL, "mmx_rollout_dagger: the policy's action width is not 4");
+  if (policy->device != sim->cfg.device) return fail(sim, MMX_EINVAL, "mmx_rollout_dagger: the policy was created on another device");
+  // (written so that a NaN fails every test)
+  if (!(cfg->beta >= 0.f && cfg->beta <= 1.f)) return fail(sim, MMX_EINVAL, "mmx_rollout_dagger: beta outside [0, 1]");
+  if (!(cfg->takeover_dist >= 0.f && cfg->takeover_dist <= FLT_MAX))
+    return fail(sim, MMX_EINVAL, "mmx_rollout_dagger: takeover_dist negative or not finite");
+  const MMXTraj R = traj_arg(rec);
+  MmxPolicy P = policy->P;
+  P.call_lo = (uint32_t)call, P.call_hi = (uint32_t)(call >> 32);
+  // the learner's row: the caller's policy_action, or the actions array itself (read back before it is overwritten)
+  float* const learner = drec->policy_action ? drec->policy_action : drec->actions;
+  const MMXPolicyRec PR{learner, drec->mean, drec->noise};
+  const MMXDagger D{drec->actions, drec->expert_action, learner, drec->gate, drec->obs_in, cfg->beta, cfg->takeover_dist};
+  const auto launch = step_launchers(sim).dagger;
+  return rollout(sim, n_env_steps, "mmx_rollout_dagger", false,
+                 [&](const MMXState* S, int base, int count, int ns, int k0, hipStream_t st, const int* ord, const MMXBudget*) {
+                   return launch(S, &R, &P, &PR, &D, base, count, ns, k0, st, ord);
                  });
 }
 

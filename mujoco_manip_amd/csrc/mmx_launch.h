@@ -13,6 +13,7 @@ struct MppiParams;
 struct MppiBufs;
 struct MmxPolicy;
 struct MMXPolicyRec;
+struct MMXDagger;
 
 extern "C" {
 
@@ -25,7 +26,10 @@ extern "C" {
                                   int base, int count, int nsteps, int k0, hipStream_t st, const int* order);          \
   hipError_t mmx_launch_physics##sfx(const MMXState* S, int n, int with_ik, hipStream_t st);                           \
   hipError_t mmx_launch_policy##sfx(const MMXState* S, const MMXTraj* R, const MmxPolicy* P, const MMXPolicyRec* PR,   \
-                                    int base, int count, int nsteps, int k0, hipStream_t st, const int* order);
+                                    int base, int count, int nsteps, int k0, hipStream_t st, const int* order);  \
+  hipError_t mmx_launch_dagger##sfx(const MMXState* S, const MMXTraj* R, const MmxPolicy* P, const MMXPolicyRec* PR,   \
+                                    const MMXDagger* D, int base, int count, int nsteps, int k0, hipStream_t st,       \
+                                    const int* order);
 MMX_DECLARE_STEP_LAUNCHERS()
 MMX_DECLARE_STEP_LAUNCHERS(_l192)
 #undef MMX_DECLARE_STEP_LAUNCHERS

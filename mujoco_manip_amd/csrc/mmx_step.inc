@@ -17,9 +17,9 @@
 // Physics follows MuJoCo's documented pipeline (the fp64 oracle in oracle/ is the checker).
 //
 // This file is everything that is compiled once per LDS-row layout: the LDS record (EnvSh), the phases,
-// substep / step_begin / step_finish, the five step kernels (mmx_env_step_kernel, its budgeted form on the
-// one-wave layout, mmx_env_traj_kernel, mmx_env_policy_kernel, and the one-substep kernel of the physics
-// harness) and their launchers.  It is included, never compiled on its own: by mmx_kernels.hip at the default
+// substep / step_begin / step_finish, the six step kernels (mmx_env_step_kernel, its budgeted form on the
+// one-wave layout, mmx_env_traj_kernel, mmx_env_policy_kernel, mmx_env_dagger_kernel, and the one-substep kernel
+// of the physics harness) and their launchers.  It is included, never compiled on its own: by mmx_kernels.hip at the default
 // MMX_LDSEFC = 128, which adds the kernels that exist once (forward, reset, expert, reward, queue, order), and
 // by mmx_step_l192.hip at 192 rows with MMX_STEP_SUFFIX _l192 on the kernels' and launchers' names
 // (MMX_STEP_SYM).
@@ -54,6 +54,7 @@
 #include "mmx_state.h"
 #include "mmx_launch.h"
 #include "mmx_policy.h"
+#include "mmx_dagger.h"
 
 #define WG 64  // lanes of the wave that runs a phase
 // lane within the wave (a workgroup is one wave: one env)

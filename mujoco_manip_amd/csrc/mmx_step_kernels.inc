@@ -1,9 +1,10 @@
 // Part 8 of mmx_step.inc, its last (an ordered fragment, included there and nowhere else): the end of an env
 // step (step_end), the out-of-line substep / step_begin / step_finish, the profile build's stamps, the helper
-// wave's loop (MMX_HELPER_WAVE_STEPS), the four fused step kernels and the one-substep kernel, and their
+// wave's loop (MMX_HELPER_WAVE_STEPS), the five fused step kernels and the one-substep kernel, and their
 // launchers.  Relies on every part before it: the record g_E and the scratch map (lds), kinematics_wave /
 // dynamics_wave (dynamics), the collide_* passes (collision), ik_wave and mj_step_wave (integrate), EPI / EPF,
-// the task layer and load_env / store_env / store_obs (task), and on mmx_policy.h for policy_act.
+// the task layer and load_env / store_env / store_obs (task), on mmx_policy.h for policy_act and on mmx_dagger.h
+// for dagger_begin.
 // ============================================================================ kernels
 // One env per 64-lane workgroup.  mmx_env_step_kernel (below) is the product path: a whole gym
 // step per launch.  mmx_substep_kernel runs ONE substep per launch (the physics-level parity
@@ -214,13 +215,13 @@ static __device__ double g_fsm_prof[11 * FSMP_N];
 
 #if MMX_STEP_HELPER
 // The helper wave's side of `nsteps` env steps of a fused step kernel (192 rows: threads 64..127), stated once
-// for mmx_env_step_kernel, mmx_env_traj_kernel and mmx_env_policy_kernel, which use it inside their
-// `if (threadIdx.x >= 64) { ...; return; }`.  It crosses exactly the workgroup barriers of the env wave's step
+// for mmx_env_step_kernel, mmx_env_traj_kernel, mmx_env_policy_kernel and mmx_env_dagger_kernel, which use it
+// inside their `if (threadIdx.x >= 64) { ...; return; }`.  It crosses exactly the workgroup barriers of the env wave's step
 // loop, no path of either wave skipping one: between two steps the fence and the barrier behind the record
 // stores, then the barrier after step_begin's record load, then per substep C, K, A, P, Q, the table in
 // mj_step_wave (mmx_step_integrate.inc), with the helper's work between them: the IK in C..K, the dynamics in
 // A..P, the GJK / EPA pairs in P..Q.  What a kernel's env wave adds around step_begin and step_finish --
-// policy_act before, traj_record after -- holds no workgroup barrier, so the helper has nothing to mirror
+// policy_act before, traj_record after, dagger_begin in step_begin's place -- holds no workgroup barrier, so the helper has nothing to mirror
 // for it: it waits at the record-load barrier meanwhile.  mmx_substep_kernel follows the same sequence for
 // its one substep.
 // A macro, not a function: the loop as one force-inlined DEV function keeps every instruction count and still
@@ -408,32 +409,42 @@ MMX_STEP_KERNEL MMX_STEP_SYM(mmx_env_traj_kernel)(MMXState S, MMXTraj R, const f
 #define POL_B0 ((POLICY_NOBS + 3) & ~3)
 #define POL_B1 (POL_B0 + POLICY_MAX_WIDTH)
 static_assert(POL_B1 + POLICY_MAX_WIDTH <= SCR_FLOATS && POLICY_NOBS == MMX_NOBS, "the policy's scratch exceeds the scratch region");
-__device__ __attribute__((noinline)) void policy_act(const MMXState& S, const MmxPolicy& P, const MMXPolicyRec& PR, int i,
-                                                     unsigned step) {
-  float* scr = scr_of(g_E);
-  const float* data = policy_data(P);
-  const float* obs = S.obs + (size_t)i * MMX_NOBS;
-  const int shift_off = policy_u(P.shift_off), scale_off = policy_u(P.scale_off);
-  for (int k = LANE; k < MMX_NOBS; k += WG) scr[POL_X + k] = policy_normalise(obs[k], data[shift_off + k], data[scale_off + k]);
-  SYNC();
-  const float* mean = policy_forward_wave(P, data, scr + POL_X, scr + POL_B0, scr + POL_B1, LANE);
-  if (LANE == 0) {
-    const int A = P.A;
-    const size_t row = ((size_t)step * (size_t)S.N + (size_t)i) * (size_t)A;
-    const float *std = data + P.std_off, *low = data + P.low_off, *high = data + P.high_off;
-    for (int a = 0; a < A; a++) {
-      const float m = mean[a];
-      float z = 0.f, act = mppi_clamp(m, low[a], high[a]);
-      if (P.stochastic) {
-        z = mppi_draw(P.seed_lo, P.seed_hi, P.call_lo, P.call_hi, step, (uint32_t)i, (uint32_t)a);
-        act = policy_action(m, std[a], z, low[a], high[a]);
-      }
-      PR.actions[row + a] = act;
-      if (PR.mean) PR.mean[row + a] = m;
-      if (PR.noise) PR.noise[row + a] = z;
-    }
+// The text is stated once, as a macro that defines one out-of-line function per kernel that calls it: policy_act
+// for mmx_env_policy_kernel, dagger_policy_act for mmx_env_dagger_kernel.  With ONE caller the optimiser knows where
+// the by-reference arguments live (the kernel's own copy of its kernel arguments) and compiles the function for it:
+// a second caller of policy_act itself changed its listing and mmx_env_policy_kernel's (tools/isa_same.py: 870 ->
+// 866 and 1125 -> 1121 instructions), and the text as a force-inlined function called from two out-of-line wrappers
+// kept the counts and changed policy_act's register allocation (as MMX_HELPER_WAVE_STEPS found); these tokens
+// pasted into each function leave both listings what the one written-out function gave.  Do not convert it.
+#define MMX_DEFINE_POLICY_ACT(name)                                                                                              \
+  __device__ __attribute__((noinline)) void name(const MMXState& S, const MmxPolicy& P, const MMXPolicyRec& PR, int i,           \
+                                                 unsigned step) {                                                                \
+    float* scr = scr_of(g_E);                                                                                                    \
+    const float* data = policy_data(P);                                                                                          \
+    const float* obs = S.obs + (size_t)i * MMX_NOBS;                                                                             \
+    const int shift_off = policy_u(P.shift_off), scale_off = policy_u(P.scale_off);                                              \
+    for (int k = LANE; k < MMX_NOBS; k += WG) scr[POL_X + k] = policy_normalise(obs[k], data[shift_off + k], data[scale_off + k]); \
+    SYNC();                                                                                                                      \
+    const float* mean = policy_forward_wave(P, data, scr + POL_X, scr + POL_B0, scr + POL_B1, LANE);                             \
+    if (LANE == 0) {                                                                                                             \
+      const int A = P.A;                                                                                                         \
+      const size_t row = ((size_t)step * (size_t)S.N + (size_t)i) * (size_t)A;                                                   \
+      const float *std = data + P.std_off, *low = data + P.low_off, *high = data + P.high_off;                                   \
+      for (int a = 0; a < A; a++) {                                                                                              \
+        const float m = mean[a];                                                                                                 \
+        float z = 0.f, act = mppi_clamp(m, low[a], high[a]);                                                                     \
+        if (P.stochastic) {                                                                                                      \
+          z = mppi_draw(P.seed_lo, P.seed_hi, P.call_lo, P.call_hi, step, (uint32_t)i, (uint32_t)a);                             \
+          act = policy_action(m, std[a], z, low[a], high[a]);                                                                    \
+        }                                                                                                                        \
+        PR.actions[row + a] = act;                                                                                               \
+        if (PR.mean) PR.mean[row + a] = m;                                                                                       \
+        if (PR.noise) PR.noise[row + a] = z;                                                                                     \
+      }                                                                                                                          \
+    }                                                                                                                            \
   }
-}
+MMX_DEFINE_POLICY_ACT(policy_act)
+MMX_DEFINE_POLICY_ACT(dagger_policy_act)
 
 // mmx_env_traj_kernel's step loop with the action of every step computed by an MLP policy from the env's own
 // observation, inside the launch (mmx_rollout_policy): step k of the launch is the rollout's step k0 + k; before
@@ -458,6 +469,71 @@ MMX_STEP_KERNEL MMX_STEP_SYM(mmx_env_policy_kernel)(MMXState S, MMXTraj R, MmxPo
     const size_t step = (size_t)(k0 + k);
     policy_act(S, P, PR, i, (unsigned)step);
     step_begin(S, i, PR.actions + step * (size_t)S.N * (size_t)P.A, P.A, 0);
+    XSYNC();
+    for (int sub = 0; sub < MMX_NSUBSTEP; sub++)
+      substep(S.solver_max_iter, S.solver_tol, sub == MMX_NSUBSTEP - 1 ? contacts_dst(S, i) : nullptr);
+    step_finish(S, i);
+    traj_record(S, R, i, step * (size_t)S.N + (size_t)i);
+  }
+}
+
+// step_begin for a DAgger step (mmx_env_dagger_kernel), out of line and without register saves like it: the
+// record load, then on lane 0 the expert's plan, the gate and the decode of the executed action, and step_begin's
+// closing SYNC() -- no workgroup barrier, so the helper wave (192 rows) mirrors nothing new.  The FSM expert plans
+// at EVERY step, whoever acts: its state only moves when it plans, so it shadows the learner exactly as
+// mmx_expert_plan(16) ahead of every mmx_step would, and the label is what that call returns at this state.
+// The learner's row is the one policy_act's lane 0 just wrote to D.policy_action (its own stores, read back; it
+// may be D.actions itself, so it is read before the executed action is written).  obs_in is the sim's observation
+// buffer as policy_act read it: nothing writes S.obs before step_finish.
+__device__ __attribute__((noinline)) void dagger_begin(const MMXState& S, const MmxPolicy& P, const MMXDagger& D, int i,
+                                                       unsigned step) {
+  EnvSh& E = g_E;
+  float* act = scr_of(E) + SCR_ACT;  // lane 0's executed action (E.J is free before the substeps)
+  const size_t row = (size_t)step * (size_t)S.N + (size_t)i;
+  if (D.obs_in)
+    for (int k = LANE; k < MMX_NOBS; k += WG) D.obs_in[row * MMX_NOBS + k] = S.obs[(size_t)i * MMX_NOBS + k];
+  load_env(S, i, E);
+  if (LANE == 0) {
+    float lab[4], pol[4];
+    expert_plan(S, i, obj_pos(E, EPI(EPI_OBJ)), hand_pos(E), MMX_NSUBSTEP, lab);
+    for (int k = 0; k < 4; k++) pol[k] = D.policy_action[row * 4 + k];
+    const float u = dagger_uniform(P.seed_lo, P.seed_hi, P.call_lo, P.call_hi, step, (uint32_t)i);
+    const int gate = dagger_gate(u, D.beta, pol, lab, D.takeover_dist);
+    dagger_select(gate, pol, lab, act);
+    for (int k = 0; k < 4; k++) {
+      D.actions[row * 4 + k] = act[k];
+      if (D.expert_action) D.expert_action[row * 4 + k] = lab[k];
+    }
+    if (D.gate) D.gate[row] = gate;
+    decode_lane0(S, i, E, act);
+  }
+  SYNC();
+}
+
+// mmx_env_policy_kernel's step loop with the FSM expert beside the learner (mmx_rollout_dagger): step k of the
+// launch is the rollout's step k0 + k; the env's wave evaluates the policy (policy_act's text, as it stands: the
+// learner's action row [k0 + k][i] of PR.actions = D.policy_action), then dagger_begin plans with the expert, records the
+// label, draws the gate and steps the env with the expert's action where the gate fires and the learner's where it
+// does not.  Everything else is that kernel's body, so states and records are bit for bit what the loop
+// mmx_expert_plan(16) -> mmx_step(D.actions[t]) gives.
+MMX_STEP_KERNEL MMX_STEP_SYM(mmx_env_dagger_kernel)(MMXState S, MMXTraj R, MmxPolicy P, MMXPolicyRec PR, MMXDagger D, int base,
+                                                    int nsteps, int k0, const int* order) {
+  const int i = order ? order[blockIdx.x] : base + blockIdx.x;
+  if (i >= S.N) return;
+#if MMX_STEP_HELPER
+  if (threadIdx.x >= 64) {  // the helper wave (the env wave runs the policy and the gate before the record-load barrier)
+    MMX_HELPER_WAVE_STEPS(nsteps)
+    return;
+  }
+#endif
+  for (int k = 0; k < nsteps; k++) {
+    if (k) {  // the previous step's record and observation stores complete before this step reads them
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+      XSYNC();
+    }
+    const size_t step = (size_t)(k0 + k);
+    dagger_policy_act(S, P, PR, i, (unsigned)step);
+    dagger_begin(S, P, D, i, (unsigned)step);
     XSYNC();
     for (int sub = 0; sub < MMX_NSUBSTEP; sub++)
       substep(S.solver_max_iter, S.solver_tol, sub == MMX_NSUBSTEP - 1 ? contacts_dst(S, i) : nullptr);
@@ -582,5 +658,16 @@ extern "C" hipError_t MMX_STEP_SYM(mmx_launch_policy)(const MMXState* S, const M
   if (!PR->actions || !P->data) return hipErrorInvalidValue;
   hipLaunchKernelGGL(MMX_STEP_SYM(mmx_env_policy_kernel), dim3(count), dim3(MMX_STEP_THREADS), step_lds_pad(), st, *S, *R, *P, *PR,
                      base, nsteps, k0, order);
+  return hipGetLastError();
+}
+// `nsteps` DAgger env steps of envs [base, base+count) from the rollout's step k0 on: the policy P acts or the FSM
+// expert does, by the gate of D; PR->actions is the learner's row and must be D->policy_action (a four-wide policy)
+extern "C" hipError_t MMX_STEP_SYM(mmx_launch_dagger)(const MMXState* S, const MMXTraj* R, const MmxPolicy* P,
+                                                      const MMXPolicyRec* PR, const MMXDagger* D, int base, int count,
+                                                      int nsteps, int k0, hipStream_t st, const int* order) {
+  if (count <= 0 || nsteps <= 0) return hipSuccess;
+  if (!D->actions || !D->policy_action || PR->actions != D->policy_action || !P->data || P->A != 4) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(MMX_STEP_SYM(mmx_env_dagger_kernel), dim3(count), dim3(MMX_STEP_THREADS), step_lds_pad(), st, *S, *R, *P, *PR,
+                     *D, base, nsteps, k0, order);
   return hipGetLastError();
 }

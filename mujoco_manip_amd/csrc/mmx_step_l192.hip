@@ -4,6 +4,7 @@
 //   mmx_env_step_kernel_l192    / mmx_launch_step_l192      env steps, host actions or the FSM expert
 //   mmx_env_traj_kernel_l192    / mmx_launch_traj_l192      env steps with an action row and a record per step
 //   mmx_env_policy_kernel_l192  / mmx_launch_policy_l192    env steps with an MLP policy's actions
+//   mmx_env_dagger_kernel_l192  / mmx_launch_dagger_l192    env steps with the policy or the FSM expert, by a gate
 //   mmx_substep_kernel_l192     / mmx_launch_physics_l192   the physics harness's one substep per launch
 // (the budgeted step kernel exists on the one-wave layout only).  The 128-row build (twelve per CU) wins once the
 // batch fills the workgroup slots; with four or fewer envs per CU each env's own speed is what counts

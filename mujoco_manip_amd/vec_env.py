@@ -25,6 +25,7 @@ import torch
 
 from . import _lib
 from .constants import ACTION_REPEAT, BINS, IMAGE_SIZE, MAX_EPISODE_STEPS, OBJECTS, OBS_SLICES, TASK_SETS, task_index
+from .dagger import DEFAULT_RECORD as DAGGER_RECORD, check_args as check_dagger_args
 
 
 def split_obs(flat: torch.Tensor) -> dict:
@@ -232,6 +233,38 @@ class PickPlaceVecEnv:
         if T == 0:
             return out
         dev.rollout(self.sim, T, call, prec, rec)
+        self._last_action = out["actions"]
+        return out
+
+    def rollout_dagger(self, policy, n_steps: int, beta: float = 0.5, takeover_dist: float = 0.0,
+                       record=DAGGER_RECORD, call: int = 0) -> dict:
+        """n_steps DAgger env steps (abs_pos envs) in the fused launches of rollout_policy: at every step the env's
+        wave evaluates the bound MlpPolicy on the observation the env holds, the FSM expert plans beside it (at
+        every step, whoever acts: its state shadows the learner's trajectory), and a gate picks the executed action:
+        the expert's with probability `beta` per step and env (a Philox draw of (policy seed, call, step, env) that
+        no noise component uses), and, with takeover_dist > 0, also wherever the learner's xyz target lies further
+        than that from the expert's.  beta=1 is rollout(n_steps=...), beta=0 with takeover_dist=0 is
+        rollout_policy.  Returns {name: tensor [T, N, ...]} for the names in `record`: the _lib.TRAJ_FIELDS entries
+        as rollout() records them, always "actions" (what the envs were stepped with), and of _lib.DAGGER_FIELDS
+        "expert_action" (the label: what expert_plan(16) returns at that state), "policy_action", "mean", "noise",
+        "gate" (int32; bit 0 the draw, bit 1 the takeover; 0: the learner acted) and "obs_in" (the observation the
+        learner was given: it pairs with the label; dagger.DaggerBuffer aggregates the pairs).  The env ends in the
+        state of the loop expert_plan(16) -> step(actions[t]); increment `call` per call for fresh draws."""
+        T, beta, takeover_dist, names = check_dagger_args(n_steps, beta, takeover_dist, record)
+        dev = policy.device_policy
+        if policy.action_dim != self.action_dim or policy._env is not self:
+            raise ValueError("the policy must be bound to this env (MlpPolicy.bind(env))")
+        if self._action_mode != "abs_pos":
+            raise ValueError("rollout_dagger needs action_mode abs_pos (the FSM expert's actions)")
+        out, rec, drec = {}, _lib.MMXTrajectory(), _lib.MMXDaggerRecord()
+        for name in names + (() if "actions" in names else ("actions",)):
+            width, dtype = _lib.DAGGER_FIELDS[name] if name in _lib.DAGGER_FIELDS else _lib.TRAJ_FIELDS[name]
+            shape = (T, self.num_envs, width) if width > 1 else (T, self.num_envs)
+            out[name] = torch.empty(shape, dtype=getattr(torch, dtype), device=self.device)
+            setattr(drec if name in _lib.DAGGER_FIELDS else rec, name, out[name].data_ptr())
+        if T == 0:
+            return out
+        dev.rollout_dagger(self.sim, T, call, _lib.MMXDaggerConfig(beta=beta, takeover_dist=takeover_dist), drec, rec)
         self._last_action = out["actions"]
         return out
 

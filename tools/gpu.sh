@@ -31,6 +31,8 @@
 #   policy           closed-loop policy rollout timing (tools/policy_time.py): the obs -> torch MLP -> step loop,
 #                    rollout_policy, and the replay of its recorded actions; BASELINE_LIB = a library of the
 #                    baseline commit for the loop; POLICY_OUT = a file for the full result
+#   dagger           DAgger rollout timing (tools/dagger_time.py): rollout_policy beside rollout_dagger at beta = 0,
+#                    interleaved on this build; DAGGER_OUT = a file for the full result
 # Env: R (round tag, default r06), MMX_LIB_PATH (a library other than the product for every recipe).
 set -o pipefail
 cd ${GRAFT_REPO_ROOT:-$(pwd)}; ROOT=$(pwd); mkdir -p gpurun_out
@@ -165,6 +167,7 @@ for recipe in "$@"; do
     occupancy) occupancy ;;
     traj) traj ;;
     policy) policy ;;
+    dagger) timeout -k 10 500 python -u tools/dagger_time.py ${DAGGER_OUT:+--out $DAGGER_OUT} ;;
     snapshot) timeout -k 10 300 python -u tools/snapshot_time.py ${SNAP_OUT:+--out $SNAP_OUT} ;;
     *) echo "unknown recipe $recipe"; false ;;
   esac || exit $?

@@ -14,7 +14,9 @@ FUNCS = ("_Z7substepifPf", "mmx_env_step_kernel", "mmx_env_step_budget_kernel", 
          "_Z10step_beginRK8MMXStateiPKfii",
          "_Z11step_finishRK8MMXStatei", "mmx_env_traj_kernel", "mmx_env_traj_kernel_l192",
          "_Z10policy_actRK8MMXStateRK9MmxPolicyRK12MMXPolicyRecij", "mmx_env_policy_kernel",
-         "mmx_env_policy_kernel_l192")  # (a listing holds one layout's kernels: the other's are left out)
+         "mmx_env_policy_kernel_l192", "_Z17dagger_policy_actRK8MMXStateRK9MmxPolicyRK12MMXPolicyRecij",
+         "_Z12dagger_beginRK8MMXStateRK9MmxPolicyRK9MMXDaggerij", "mmx_env_dagger_kernel",
+         "mmx_env_dagger_kernel_l192")  # (a listing holds one layout's kernels: the other's are left out)
 
 # a function's label: `name:` in a -S listing, `0000000000001900 <name>:` in llvm-objdump -d output
 LABEL = re.compile(r"^(?:[0-9a-f]+ <)?([A-Za-z_][\w.$]*)>?:\s*(;.*)?$")
@@ -47,8 +49,8 @@ def frames(path):
     out = {}
     for f in FUNCS:
         seg = re.search(rf"\.set (?:\.L)?{re.escape(f)}\.private_seg_size, (\d+)(\+max)?", txt)
-        if not seg and f.startswith("_Z10policy_act"):
-            continue  # (a listing of before the policy kernel)
+        if not seg and f.startswith(("_Z10policy_act", "_Z17dagger_policy_act", "_Z12dagger_begin")):
+            continue  # (a listing of before the policy kernel, or the DAgger kernel)
         vg = re.search(rf"\.set (?:\.L)?{re.escape(f)}\.num_vgpr, (?:max\()?(\d+)", txt)
         if f.startswith("mmx_env_") and not seg:
             continue
