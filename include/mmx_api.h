@@ -369,6 +369,53 @@ int  mmx_policy_eval(mmx_policy* p, const float* obs_dev, int32_t n, float* mean
 int  mmx_rollout_policy(mmx_sim* sim, mmx_policy* policy, int32_t n_env_steps, uint64_t call,
                         const mmx_policy_record* prec, const mmx_trajectory* rec);
 
+/* Fitting a policy on the device (no reference counterpart): minibatch gradient steps of the mean-squared error
+ * between the network's output (mean: before noise and clamp) and given targets, which update the policy's packed
+ * weights in place on the creating sim's stream; the next mmx_rollout_policy, mmx_rollout_dagger or mmx_policy_eval
+ * on that stream runs the new weights with nothing in between.  Every layer's weights and biases are trained (a
+ * bias that was NULL at create starts from 0); obs_shift, obs_scale, log_std, low and high are not.
+ *     L = 1 / (B A) sum_{s < B, a < A} (mean(obs[p_s])[a] - target[p_s][a])^2,   B = cfg->batch
+ * Optimisation step k (k = t - 1; t counts the policy's steps from 1 across calls) draws pair p_s of sample s as
+ *     shuffle 0: (k B + s) mod n_pairs (sequential sweeps);
+ *     shuffle 1: (uint64(x) n_pairs) >> 32, x = word s % 4 of Philox4x32-10 with key = cfg->seed and counter =
+ *                (k low, k high, s / 4, 0xF17BA7C4): with replacement, a function of (seed, k, s) alone.
+ * MMX_FIT_SGD: w = fma(-lr, g, w).  MMX_FIT_ADAM (torch.optim.Adam's defaults: no weight decay, no amsgrad), one
+ * rounding per operation: m = fma(beta1, m, (1 - beta1) g); v = fma(beta2, v, ((1 - beta2) g) g); w = w - (lr (m c1))
+ * / (sqrt(v c2) + eps), c1 = 1 / (1 - beta1^t) and c2 = 1 / (1 - beta2^t) evaluated per step on the host in fp64 and
+ * rounded to fp32; IEEE square root and division.  m, v and t belong to the policy and persist across calls;
+ * cfg->reset_optimizer = 1 zeroes them before the call's first step.  SGD advances t too (it numbers the batches).
+ * Everything is fp32; the gradient sums run over the samples in a fixed order (tiles of 16 samples, chunks of 512,
+ * then chunk by chunk): there are no atomics, and the same call on the same state gives the same bits every time.
+ * mmx_policy_fit: obs_dev [n_pairs][85], target_dev [n_pairs][A] (device pointers, read by every step's launches:
+ * keep them unchanged until the stream has run them); n_steps optimisation steps are queued without a host
+ * synchronisation; loss_out_dev [n_steps] (device) or NULL: loss_out[i] = the batch loss before update i of this
+ * call.  The first call allocates the workspace (activations, deltas, partial sums, m, v) and a later call with a
+ * larger batch synchronises the stream and grows it; mmx_policy_create allocates none of it, mmx_policy_destroy
+ * frees it.  A policy shared by several sims is fitted on its creator's stream only: ordering against rollouts of
+ * the other sims (other streams) is the caller's responsibility.
+ * MMX_EINVAL, with nothing touched, for a NULL p, obs_dev, target_dev or cfg, n_pairs < 1 or > 2^31 - 1, n_steps < 0
+ * (0 does nothing), batch outside 1 .. MMX_FIT_MAX_BATCH, an unknown optimizer, lr or eps not finite or <= 0,
+ * beta1 or beta2 outside [0, 1).
+ * mmx_policy_get_weights: synchronises the stream and copies the layers out in mmx_policy_config's layout
+ * (weight_host[l] [width[l]][inputs], bias_host[l] [width[l]]; host pointers; bias_host or an entry of either NULL:
+ * skipped).  mmx_policy_set_weights: the reverse, in place on the stream (returns when the copy is done; a NULL
+ * bias_host or bias_host[l]: zeros; every weight_host[l] required); m, v and t stay as they are. */
+#define MMX_FIT_SGD 0
+#define MMX_FIT_ADAM 1
+#define MMX_FIT_MAX_BATCH 65536
+typedef struct {
+  int32_t optimizer;       /* MMX_FIT_SGD | MMX_FIT_ADAM */
+  int32_t batch;           /* 1 .. MMX_FIT_MAX_BATCH */
+  int32_t shuffle;         /* 0: sequential sweeps, 1: Philox draws with replacement */
+  int32_t reset_optimizer; /* 1: zero m, v and t before the first step of this call */
+  float lr, beta1, beta2, eps;
+  uint64_t seed;
+} mmx_fit_config;
+int  mmx_policy_fit(mmx_policy* p, const float* obs_dev, const float* target_dev, int64_t n_pairs, int32_t n_steps,
+                    const mmx_fit_config* cfg, float* loss_out_dev);
+int  mmx_policy_get_weights(mmx_policy* p, float* const* weight_host, float* const* bias_host);
+int  mmx_policy_set_weights(mmx_policy* p, const float* const* weight_host, const float* const* bias_host);
+
 /* DAgger rollouts (Ross et al. 2011; no reference counterpart): mmx_rollout_policy with the FSM expert beside the
  * learner, in the same fused launches (lanes, launch plan, dispatch order, both camera paths; with cameras the
  * numeric observation is read and the images hold the last frame).  Per rollout step t and env i, inside the launch:

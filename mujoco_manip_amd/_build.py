@@ -15,7 +15,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libmmx.so")
 LIB_PROF = os.path.join(PKG, "libmmx_prof.so")
 SOURCES = ["mmx_kernels.hip", "mmx_step_l192.hip", "mmx_render.hip", "mmx_render_lit.hip", "mmx_png.hip",
-           "mmx_snapshot.hip", "mmx_mppi.hip", "mmx_policy.hip", "mmx_api.cpp"]
+           "mmx_snapshot.hip", "mmx_mppi.hip", "mmx_policy.hip", "mmx_policy_fit.hip", "mmx_api.cpp"]
 ARCH = os.environ.get("MMX_OFFLOAD_ARCH", "gfx950")
 # device-code math: x / y as x * rcp(y) and sqrt without the denormal-scaling wrapper (v_rcp_f32 /
 # v_sqrt_f32, <= 1 ulp) instead of the correctly rounded fdiv / sqrt expansions (~10 VALU each).
@@ -49,9 +49,12 @@ FLAGS = DEVICE_MATH + DEVICE_SCHED + DEVICE_NOSLP + os.environ.get("MMX_EXTRA_FL
 # non-finite return is plain C++ on the bits of a value the compiler saw computed, and under
 # -ffinite-math-only it folds to "finite" (the step kernel hides its values behind an opaque register copy
 # instead; these kernels use no inline assembly).  Same registers, no scratch; they are no hot path.
+# The policy's training step keeps IEEE division and square root: Adam's update is stated operation by operation
+# (csrc/mmx_policy_fit.h) and the device computes it as the host does.
 SOURCE_FLAGS = {"mmx_kernels.hip": ["-Xarch_device", "-fassociative-math"],
                 "mmx_step_l192.hip": ["-Xarch_device", "-fassociative-math"],
-                "mmx_mppi.hip": ["-Xarch_device", "-fno-finite-math-only"]}
+                "mmx_mppi.hip": ["-Xarch_device", "-fno-finite-math-only"],
+                "mmx_policy_fit.hip": ["-Xarch_device", "-fno-reciprocal-math", "-Xarch_device", "-fno-approx-func"]}
 
 
 # test-only builds of the step kernel (tests/test_overflow_kat.py, tests/test_helper_layout.py): both

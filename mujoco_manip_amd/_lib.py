@@ -133,6 +133,17 @@ class MMXPolicyRecord(C.Structure):
     _fields_ = [("actions", C.c_void_p), ("mean", C.c_void_p), ("noise", C.c_void_p)]
 
 
+# include/mmx_api.h MMX_FIT_SGD / MMX_FIT_ADAM, MMX_FIT_MAX_BATCH
+FIT_OPTIMIZERS = ("sgd", "adam")
+FIT_MAX_BATCH = 65536
+
+
+class MMXFitConfig(C.Structure):
+    """mmx_fit_config (include/mmx_api.h): one mmx_policy_fit call's optimiser and batch selection."""
+    _fields_ = [("optimizer", C.c_int32), ("batch", C.c_int32), ("shuffle", C.c_int32), ("reset_optimizer", C.c_int32),
+                ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("seed", C.c_uint64)]
+
+
 class MMXDaggerConfig(C.Structure):
     """mmx_dagger_config (include/mmx_api.h): the gate of mmx_rollout_dagger."""
     _fields_ = [("beta", C.c_float), ("takeover_dist", C.c_float)]
@@ -212,6 +223,9 @@ _PROTOS = {
     "mmx_policy_destroy": (None, [_vp]),
     "mmx_policy_eval": (C.c_int, [_vp, _vp, _i32, _vp]),
     "mmx_rollout_policy": (C.c_int, [_vp, _vp, _i32, C.c_uint64, C.POINTER(MMXPolicyRecord), C.POINTER(MMXTrajectory)]),
+    "mmx_policy_fit": (C.c_int, [_vp, _vp, _vp, _i64, _i32, C.POINTER(MMXFitConfig), _vp]),
+    "mmx_policy_get_weights": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "mmx_policy_set_weights": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "mmx_rollout_dagger": (C.c_int, [_vp, _vp, _i32, C.c_uint64, C.POINTER(MMXDaggerConfig), C.POINTER(MMXDaggerRecord),
                                      C.POINTER(MMXTrajectory)]),
     "mmx_png_bound": (_i64, [_i32, _i32]),
@@ -800,6 +814,7 @@ class Policy(_Owner):
         cfg.low, cfg.high = ptr(low), ptr(high)
         self.sim, self.L = sim, sim.L
         self.action_dim = int(np.shape(layers[-1][0])[0]) if layers else 0
+        self.shapes = [tuple(int(v) for v in np.shape(W)) for W, _ in layers]  # [(out, in), ...]
         out = C.c_void_p()
         rc = self.L.mmx_policy_create(sim.ptr, C.byref(cfg), C.byref(out))
         if rc != 0 or not out.value:
@@ -810,6 +825,36 @@ class Policy(_Owner):
         """mean [n][A] at out_ptr of the observations [n][85] at obs_ptr (device pointers; mmx_policy_eval,
         asynchronous on the creating sim's stream)."""
         self.sim._check(self.L.mmx_policy_eval(self.ptr, C.c_void_p(obs_ptr), int(n), C.c_void_p(out_ptr)), "mmx_policy_eval")
+
+    def fit(self, obs_ptr: int, target_ptr: int, n_pairs: int, n_steps: int, cfg: MMXFitConfig, loss_ptr: int | None = None):
+        """n_steps optimisation steps on the pairs (obs [n][85], target [n][A]: device pointers) that update the
+        weights in place; loss_ptr: device [n_steps] or None (mmx_policy_fit, asynchronous on the creating sim's
+        stream)."""
+        self.sim._check(self.L.mmx_policy_fit(self.ptr, C.c_void_p(obs_ptr), C.c_void_p(target_ptr), int(n_pairs), int(n_steps),
+                                              C.byref(cfg), C.c_void_p(loss_ptr) if loss_ptr else None), "mmx_policy_fit")
+
+    def get_weights(self) -> list:
+        """[(W [out, in], b [out]), ...] float32 numpy arrays of the weights as they are now (mmx_policy_get_weights;
+        synchronises the creating sim's stream)."""
+        layers = [(np.empty(shp, np.float32), np.empty(shp[0], np.float32)) for shp in self.shapes]
+        wp = (C.c_void_p * POLICY_MAX_LAYERS)(*[W.ctypes.data for W, _ in layers])
+        bp = (C.c_void_p * POLICY_MAX_LAYERS)(*[b.ctypes.data for _, b in layers])
+        self.sim._check(self.L.mmx_policy_get_weights(self.ptr, wp, bp), "mmx_policy_get_weights")
+        return layers
+
+    def set_weights(self, layers):
+        """The reverse: layers [(W [out, in], b [out] or None), ...] of the policy's own shapes into the device
+        blob, in place (mmx_policy_set_weights); the optimiser's state stays."""
+        if len(layers) != len(self.shapes):
+            raise ValueError(f"the policy has {len(self.shapes)} layers, got {len(layers)}")
+        keep = []
+        for k, ((W, b), shp) in enumerate(zip(layers, self.shapes)):
+            if tuple(np.shape(W)) != shp or (b is not None and tuple(np.shape(b)) != (shp[0],)):
+                raise ValueError(f"layers[{k}] must be ([{shp[0]}, {shp[1]}], [{shp[0]}] or None)")
+            keep.append((np.ascontiguousarray(W, np.float32), None if b is None else np.ascontiguousarray(b, np.float32)))
+        wp = (C.c_void_p * POLICY_MAX_LAYERS)(*[W.ctypes.data for W, _ in keep])
+        bp = (C.c_void_p * POLICY_MAX_LAYERS)(*[None if b is None else b.ctypes.data for _, b in keep])
+        self.sim._check(self.L.mmx_policy_set_weights(self.ptr, wp, bp), "mmx_policy_set_weights")
 
     def rollout(self, sim: Sim, n_env_steps: int, call: int, prec: MMXPolicyRecord, record: MMXTrajectory | None = None):
         """n_env_steps closed-loop env steps of `sim` under this policy in fused launches (mmx_rollout_policy)."""

@@ -21,6 +21,7 @@
 #include "mmx_mppi.h"
 #include "mmx_plan.h"
 #include "mmx_policy.h"
+#include "mmx_policy_fit.h"
 #include "mmx_seed.h"
 #include "mmx_state.h"
 
@@ -116,6 +117,13 @@ struct mmx_policy {
   int device = 0;  // the sim's (kept for mmx_policy_destroy and mmx_rollout_policy's check)
   MmxPolicy P{};
   float* data = nullptr;
+  // mmx_policy_fit's state, allocated at the first fit: the optimiser's m and v (indexed like the blob's layers),
+  // its step counter t (0: no step yet), and the workspace of a batch of up to fit_batch samples
+  float* fit_m = nullptr;
+  float* fit_v = nullptr;
+  float* fit_ws = nullptr;
+  int fit_batch = 0;
+  uint64_t fit_t = 0;
 };
 
 namespace {
@@ -1089,6 +1097,8 @@ void mmx_policy_destroy(mmx_policy* p) {
   if (!p) return;
   DeviceGuard guard(p->device);
   if (p->data) (void)hipFree(p->data);
+  for (float* a : {p->fit_m, p->fit_v, p->fit_ws})
+    if (a) (void)hipFree(a);
   delete p;
 }
 
@@ -1097,6 +1107,112 @@ int mmx_policy_eval(mmx_policy* p, const float* obs_dev, int32_t n, float* mean_
   if (!obs_dev || !mean_out_dev || n < 0) return fail(p->sim, MMX_EINVAL, "mmx_policy_eval: NULL argument or n < 0");
   DeviceGuard guard(p->sim);
   return hip_check(p->sim, mmx_launch_policy_eval(&p->P, obs_dev, n, mean_out_dev, p->sim->stream), "mmx_policy_eval");
+}
+
+// The policy's training step (mmx_policy_fit.h; mmx_policy_fit.hip): n_steps times three launches on the stream
+int mmx_policy_fit(mmx_policy* p, const float* obs_dev, const float* target_dev, int64_t n_pairs, int32_t n_steps,
+                   const mmx_fit_config* c, float* loss_out_dev) {
+  if (!p) return MMX_EINVAL;
+  mmx_sim* sim = p->sim;
+  if (!obs_dev || !target_dev || !c) return fail(sim, MMX_EINVAL, "mmx_policy_fit: NULL argument");
+  if (n_pairs < 1 || n_pairs > INT32_MAX || n_steps < 0) return fail(sim, MMX_EINVAL, "mmx_policy_fit: n_pairs outside 1 .. 2^31 - 1 or n_steps < 0");
+  if (c->batch < 1 || c->batch > MMX_FIT_MAX_BATCH) return fail(sim, MMX_EINVAL, "mmx_policy_fit: batch outside 1 .. 65536");
+  if (c->optimizer != MMX_FIT_SGD && c->optimizer != MMX_FIT_ADAM) return fail(sim, MMX_EINVAL, "mmx_policy_fit: unknown optimizer");
+  // (written so that a NaN fails every test)
+  if (!(c->lr > 0.f && c->lr <= FLT_MAX) || !(c->eps > 0.f && c->eps <= FLT_MAX))
+    return fail(sim, MMX_EINVAL, "mmx_policy_fit: lr or eps not finite or <= 0");
+  if (!(c->beta1 >= 0.f && c->beta1 < 1.f) || !(c->beta2 >= 0.f && c->beta2 < 1.f))
+    return fail(sim, MMX_EINVAL, "mmx_policy_fit: a beta outside [0, 1)");
+  if (n_steps == 0) return MMX_OK;
+  DeviceGuard guard(sim);
+  const MmxPolicy& P = p->P;
+  const size_t params = policy_fit_param_floats(P);
+  if (!p->fit_m) {
+    void *m = nullptr, *v = nullptr;
+    if (hipMalloc(&m, params * sizeof(float)) != hipSuccess || hipMalloc(&v, params * sizeof(float)) != hipSuccess) {
+      if (m) (void)hipFree(m);
+      return fail(sim, MMX_ENOMEM, "mmx_policy_fit: device allocation");
+    }
+    p->fit_m = static_cast<float*>(m), p->fit_v = static_cast<float*>(v);
+    if (hipMemsetAsync(m, 0, params * sizeof(float), sim->stream) != hipSuccess ||
+        hipMemsetAsync(v, 0, params * sizeof(float), sim->stream) != hipSuccess)
+      return fail(sim, MMX_EDEVICE, "mmx_policy_fit: clearing the optimiser state");
+  }
+  if (c->batch > p->fit_batch) {
+    if (p->fit_ws) {  // launches queued by an earlier call may still use it
+      if (hipStreamSynchronize(sim->stream) != hipSuccess) return fail(sim, MMX_EDEVICE, "mmx_policy_fit sync");
+      (void)hipFree(p->fit_ws);
+      p->fit_ws = nullptr, p->fit_batch = 0;
+    }
+    void* w = nullptr;
+    if (hipMalloc(&w, mmx_policy_fit_workspace_floats(&P, c->batch, nullptr) * sizeof(float)) != hipSuccess)
+      return fail(sim, MMX_ENOMEM, "mmx_policy_fit: device allocation (workspace)");
+    p->fit_ws = static_cast<float*>(w), p->fit_batch = c->batch;
+  }
+  if (c->reset_optimizer) {
+    if (hipMemsetAsync(p->fit_m, 0, params * sizeof(float), sim->stream) != hipSuccess ||
+        hipMemsetAsync(p->fit_v, 0, params * sizeof(float), sim->stream) != hipSuccess)
+      return fail(sim, MMX_EDEVICE, "mmx_policy_fit: clearing the optimiser state");
+    p->fit_t = 0;
+  }
+  MmxFit F{};
+  F.obs = obs_dev, F.target = target_dev, F.n = n_pairs, F.ws = p->fit_ws;
+  (void)mmx_policy_fit_workspace_floats(&P, c->batch, &F);
+  F.seed_lo = (uint32_t)c->seed, F.seed_hi = (uint32_t)(c->seed >> 32);
+  F.B = c->batch, F.shuffle = c->shuffle != 0;
+  F.inv_count = policy_fit_inv_count(c->batch, P.A), F.dscale = 2.f * F.inv_count;
+  for (int32_t i = 0; i < n_steps; i++) {
+    F.k = p->fit_t++;
+    const MmxFitOpt O = policy_fit_opt(c->optimizer, c->lr, c->beta1, c->beta2, c->eps, p->fit_t);
+    const hipError_t e = mmx_launch_policy_fit_step(&P, &F, &O, p->data, p->fit_m, p->fit_v,
+                                                    loss_out_dev ? loss_out_dev + i : nullptr, sim->stream);
+    if (e != hipSuccess) return hip_check(sim, e, "mmx_policy_fit");
+  }
+  return MMX_OK;
+}
+
+int mmx_policy_get_weights(mmx_policy* p, float* const* weight_host, float* const* bias_host) {
+  if (!p) return MMX_EINVAL;
+  if (!weight_host && !bias_host) return fail(p->sim, MMX_EINVAL, "mmx_policy_get_weights: NULL arguments");
+  DeviceGuard guard(p->sim);
+  const MmxPolicy& P = p->P;
+  std::vector<float> blob(policy_fit_param_floats(P));
+  if (hipStreamSynchronize(p->sim->stream) != hipSuccess ||
+      hipMemcpy(blob.data(), p->data, blob.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(p->sim, MMX_EDEVICE, "mmx_policy_get_weights: readback");
+  for (int l = 0; l < P.n_layers; l++) {
+    const int in = P.in[l], out = P.out[l];
+    for (int j = 0; j < out; j++) {
+      if (weight_host && weight_host[l])
+        for (int k = 0; k < in; k++) weight_host[l][(size_t)j * (size_t)in + (size_t)k] = blob[(size_t)P.woff[l] + policy_windex(out, k, j)];
+      if (bias_host && bias_host[l]) bias_host[l][j] = blob[(size_t)P.boff[l] + (size_t)j];
+    }
+  }
+  return MMX_OK;
+}
+
+int mmx_policy_set_weights(mmx_policy* p, const float* const* weight_host, const float* const* bias_host) {
+  if (!p) return MMX_EINVAL;
+  const MmxPolicy& P = p->P;
+  bool ok = weight_host != nullptr;
+  for (int l = 0; l < P.n_layers && ok; l++) ok = weight_host[l] != nullptr;
+  if (!ok) return fail(p->sim, MMX_EINVAL, "mmx_policy_set_weights: a NULL weight");
+  DeviceGuard guard(p->sim);
+  // the layers' part of the blob, packed as at create: the vectors behind it (shift .. high) are not touched
+  std::vector<float> blob(policy_fit_param_floats(P));
+  for (int l = 0; l < P.n_layers; l++) {
+    const int in = P.in[l], out = P.out[l], outp = policy_padded(out);
+    const float* b = bias_host ? bias_host[l] : nullptr;
+    for (int j = 0; j < outp; j++) {
+      for (int k = 0; k < in; k++)
+        blob[(size_t)P.woff[l] + policy_windex(out, k, j)] = j < out ? weight_host[l][(size_t)j * (size_t)in + (size_t)k] : 0.f;
+      blob[(size_t)P.boff[l] + (size_t)j] = j < out && b ? b[j] : 0.f;
+    }
+  }
+  if (hipMemcpyAsync(p->data, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice, p->sim->stream) != hipSuccess ||
+      hipStreamSynchronize(p->sim->stream) != hipSuccess)
+    return fail(p->sim, MMX_EDEVICE, "mmx_policy_set_weights: upload");
+  return MMX_OK;
 }
 
 int mmx_rollout_policy(mmx_sim* sim, mmx_policy* policy, int32_t n_env_steps, uint64_t call, const mmx_policy_record* prec,

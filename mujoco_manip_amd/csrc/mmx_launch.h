@@ -1,6 +1,6 @@
 // The host seam between mmx_api.cpp and the kernel sources: every non-kernel extern "C" function that one
 // source defines and another calls, declared once.  mmx_api.cpp includes it and so does every source that
-// defines one of them (mmx_step.inc, whose launchers are in mmx_step_kernels.inc, mmx_render.hip, mmx_png.hip, mmx_snapshot.hip, mmx_mppi.hip, mmx_policy.hip), so a parameter list
+// defines one of them (mmx_step.inc, whose launchers are in mmx_step_kernels.inc, mmx_render.hip, mmx_png.hip, mmx_snapshot.hip, mmx_mppi.hip, mmx_policy.hip, mmx_policy_fit.hip), so a parameter list
 // changed on one side only is a compile error.  (The diagnostic exports that tools load through ctypes,
 // mmx_fsm_profile and mmx_render_clock among them, are not called across sources and are not listed.)
 #ifndef MMX_LAUNCH_H
@@ -14,6 +14,8 @@ struct MppiBufs;
 struct MmxPolicy;
 struct MMXPolicyRec;
 struct MMXDagger;
+struct MmxFit;
+struct MmxFitOpt;
 
 extern "C" {
 
@@ -89,6 +91,13 @@ hipError_t mmx_launch_mppi_fill(const MppiParams* P, float* nominal, const float
 
 // mmx_policy.hip (MmxPolicy, MMXPolicyRec: mmx_policy.h): the network alone on n observation rows, one wave each
 hipError_t mmx_launch_policy_eval(const MmxPolicy* P, const float* obs, int n, float* mean_out, hipStream_t st);
+
+// mmx_policy_fit.hip (MmxFit, MmxFitOpt: mmx_policy_fit.h): the floats of the workspace of a batch of B (F, when not
+// null, gets its three bases), and the three launches of one optimisation step; m, v: the optimiser's arrays,
+// loss_out: one float or null
+size_t mmx_policy_fit_workspace_floats(const MmxPolicy* P, int B, MmxFit* F);
+hipError_t mmx_launch_policy_fit_step(const MmxPolicy* P, const MmxFit* F, const MmxFitOpt* O, float* blob, float* m, float* v,
+                                      float* loss_out, hipStream_t st);
 
 }  // extern "C"
 

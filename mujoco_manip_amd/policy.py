@@ -130,6 +130,89 @@ class MlpPolicy:
                 dev.eval(x.data_ptr(), x.shape[0], out.data_ptr())
         return out
 
+    # ------------------------------------------------------------------ fitting on the device (mmx_policy_fit)
+    def fit(self, obs, target, steps: int, batch: int = 8192, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+            optimizer: str = "adam", shuffle: bool = True, seed: int = 0, reset_optimizer: bool = False):
+        """`steps` minibatch gradient steps of the mean-squared error between the network's output and `target` on
+        the pairs (obs [n, 85], target [n, A]: contiguous float32 torch tensors on the policy's device), which
+        update the bound policy's weights in place on the env's stream: the next rollout or eval runs them.
+        Returns the losses [steps] (a device tensor; loss[i] is the batch loss before update i).  The optimiser's
+        moments and step count persist across calls unless reset_optimizer.  self.layers keeps the weights the
+        policy was made with until weights() refreshes it."""
+        import torch
+
+        dev, env = self.device_policy, self._env
+        if optimizer not in _lib.FIT_OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of {_lib.FIT_OPTIMIZERS}, got '{optimizer}'")
+        steps, batch = int(steps), int(batch)
+        if steps < 0:
+            raise ValueError(f"steps must be >= 0, got {steps}")
+        if not 1 <= batch <= _lib.FIT_MAX_BATCH:
+            raise ValueError(f"batch must be in 1 .. {_lib.FIT_MAX_BATCH}, got {batch}")
+        for name, t, width in (("obs", obs, _lib.NOBS), ("target", target, self.action_dim)):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name} must be a torch tensor on {env.device}")
+            if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != width:
+                raise ValueError(f"{name} must be float32 [n, {width}], got {t.dtype} {tuple(t.shape)}")
+            if t.device != torch.device(env.device):
+                raise ValueError(f"{name} must be on {env.device}, got {t.device}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+        n = obs.shape[0]
+        if target.shape[0] != n or not 1 <= n < 2**31:
+            raise ValueError(f"obs and target must have the same number of rows in 1 .. 2^31 - 1, got {n} and {target.shape[0]}")
+        b1, b2 = (float(v) for v in betas)
+        if not (np.isfinite(lr) and lr > 0 and np.isfinite(eps) and eps > 0 and 0 <= b1 < 1 and 0 <= b2 < 1):
+            raise ValueError("lr and eps must be finite and > 0, betas in [0, 1)")
+        cfg = _lib.MMXFitConfig(optimizer=_lib.FIT_OPTIMIZERS.index(optimizer), batch=batch, shuffle=int(bool(shuffle)),
+                                reset_optimizer=int(bool(reset_optimizer)), lr=lr, beta1=b1, beta2=b2, eps=eps,
+                                seed=int(seed) & (2**64 - 1))
+        loss = torch.empty(steps, dtype=torch.float32, device=env.device)
+        if steps:
+            with env.sim._on_sim_stream(env.device) as (cur, sst):
+                for t in (obs, target, loss):
+                    t.record_stream(sst)
+                dev.fit(obs.data_ptr(), target.data_ptr(), n, steps, cfg, loss.data_ptr())
+        return loss
+
+    def weights(self):
+        """[(W [out, in], b [out]), ...] numpy arrays (torch layout) of the bound policy's weights as they are now;
+        self.layers becomes this list.  Waits for the env's stream."""
+        self.layers = self.device_policy.get_weights()
+        return self.layers
+
+    def to_torch(self, net):
+        """Copies the bound policy's current weights into `net`, a torch.nn.Sequential of the shape from_torch
+        takes (a Linear without a bias must belong to a layer whose bias is 0: it cannot hold one)."""
+        import torch
+
+        layers = self.weights()
+        lin = list(net)[0::2]
+        if len(lin) != len(layers) or any(tuple(m.weight.shape) != W.shape for m, (W, _) in zip(lin, layers)):
+            raise ValueError("to_torch: the net's Linear layers do not match the policy's")
+        with torch.no_grad():
+            for m, (W, b) in zip(lin, layers):
+                m.weight.copy_(torch.from_numpy(W))
+                if m.bias is not None:
+                    m.bias.copy_(torch.from_numpy(b))
+                elif np.any(b != 0):
+                    raise ValueError("to_torch: a Linear without a bias cannot take a layer whose bias is not 0")
+        return net
+
+    def load(self, net_or_layers):
+        """Sets the bound policy's weights in place from a torch.nn.Sequential (as from_torch) or from a list
+        [(W, b or None), ...] of the policy's own shapes; the optimiser's state stays."""
+        dev = self.device_policy
+        if hasattr(net_or_layers, "parameters"):
+            src = MlpPolicy.from_torch(net_or_layers)
+            if src.activation != self.activation and len(src.layers) > 1:
+                raise ValueError(f"load: the net's activation is {src.activation}, the policy's {self.activation}")
+            layers = src.layers
+        else:
+            layers = [(_f32(W, "weight"), _f32(b, "bias")) for W, b in net_or_layers]
+        dev.set_weights(layers)
+        self.layers = [(W, b) for W, b in layers]
+
     def close(self):
         if self._dev is not None:
             self._dev.close()

@@ -13,8 +13,13 @@ the rounds reach; CHANGELOG.md holds the table of one run).
      `successes` / `placed` counters of episode_i, printed as a table beside the expert's own line.  Without the
      expert's FSM an episode ends on termination or at the time limit alone (500 steps), so the learner runs past it.
 
+--fit torch (the default: the table stays comparable with CHANGELOG.md's) trains the net with torch.optim.Adam and
+makes a new device policy of it every round; --fit device keeps ONE bound MlpPolicy through all rounds and
+policy.fit(x, y, ...) (mmx_policy_fit: minibatch Adam steps in HIP, in place in the policy's device weights) replaces
+train() and the re-creation: the loop then needs torch for its tensors only.
+
   python tools/dagger_example.py [--envs 1024] [--steps 300] [--rounds 4] [--beta0 0.5] [--decay 0.5]
-                                 [--fit-steps 300] [--eval-steps 510]
+                                 [--fit-steps 300] [--eval-steps 510] [--fit torch|device]
 """
 import argparse
 import os
@@ -50,13 +55,12 @@ def counters(env, base=(0, 0, 0)):
     return tuple(int(env._epi[:, k].sum()) - b for k, b in zip((OK, PLACED, EPISODES), base))
 
 
-def learner_alone(net, shift, scale, n, steps, seed):
-    """(successes, placed, episodes ended) of `steps` env steps of the learner alone on a fresh env."""
-    from mujoco_manip_amd.policy import MlpPolicy
-
+def learner_alone(policy, n, steps, seed):
+    """(successes, placed, episodes ended) of `steps` env steps of the learner (an unbound MlpPolicy) alone on a
+    fresh env."""
     env = make_env(n, seed)
     base = counters(env)
-    policy = MlpPolicy.from_torch(net, obs_shift=shift, obs_scale=scale).bind(env)
+    policy.bind(env)
     env.rollout_policy(policy, steps, record=())
     out = counters(env, base)
     policy.close()
@@ -73,6 +77,7 @@ def main():
     ap.add_argument("--decay", type=float, default=0.5)
     ap.add_argument("--fit-steps", type=int, default=300)
     ap.add_argument("--eval-steps", type=int, default=510)
+    ap.add_argument("--fit", choices=("torch", "device"), default="torch")
     a = ap.parse_args()
     from mujoco_manip_amd.dagger import DaggerBuffer
     from mujoco_manip_amd.policy import MlpPolicy
@@ -87,25 +92,43 @@ def main():
     shift, sd = obs_e.mean(0), obs_e.std(0)
     scale = torch.where(sd > 1e-6, 1.0 / sd.clamp_min(1e-6), torch.zeros_like(sd))
     net = nn.Sequential(nn.Linear(_lib.NOBS, 256), nn.Tanh(), nn.Linear(256, 256), nn.Tanh(), nn.Linear(256, 4)).to(obs_e.device)
-    loss = train(net, (obs_e - shift) * scale, act_e, a.fit_steps)
-    rows = [("BC", "-", obs_e.shape[0], loss, "-", *learner_alone(net, shift, scale, a.envs, a.eval_steps, SEED + 1))]
-    buf = DaggerBuffer()
+    device_fit = a.fit == "device"
     env = make_env(a.envs)  # the DAgger env runs on through the rounds: the learner's own state distribution
+    # --fit device: the one policy object of the whole run, fitted in place
+    policy = MlpPolicy.from_torch(net, obs_shift=shift, obs_scale=scale).bind(env) if device_fit else None
+
+    def fit(x, y, seed):
+        if device_fit:
+            return float(policy.fit(x.contiguous(), y.contiguous(), a.fit_steps, seed=seed)[-1])
+        return train(net, (x - shift) * scale, y, a.fit_steps, seed=seed)
+
+    def learner():
+        if device_fit:
+            return MlpPolicy(policy.weights(), activation="tanh", obs_shift=shift, obs_scale=scale)
+        return MlpPolicy.from_torch(net, obs_shift=shift, obs_scale=scale)
+
+    loss = fit(obs_e, act_e, 0)
+    rows = [("BC", "-", obs_e.shape[0], loss, "-", *learner_alone(learner(), a.envs, a.eval_steps, SEED + 1))]
+    buf = DaggerBuffer()
     for k in range(a.rounds):
         beta = a.beta0 * a.decay ** k
-        policy = MlpPolicy.from_torch(net, obs_shift=shift, obs_scale=scale).bind(env)
+        if not device_fit:
+            policy = MlpPolicy.from_torch(net, obs_shift=shift, obs_scale=scale).bind(env)
         rec = env.rollout_dagger(policy, a.steps, beta=beta, call=k)
         env.synchronize()
-        policy.close()
+        if not device_fit:
+            policy.close()
         buf.add(rec)
         obs_d, act_d = buf.tensors()
         x, y = torch.cat([obs_e, obs_d]), torch.cat([act_e, act_d])
-        loss = train(net, (x - shift) * scale, y, a.fit_steps, seed=k + 1)
+        loss = fit(x, y, k + 1)
         share = float((rec["gate"] != 0).float().mean())
         rows.append((f"round {k + 1}", f"{beta:.3f}", x.shape[0], loss, f"{share:.3f}",
-                     *learner_alone(net, shift, scale, a.envs, a.eval_steps, SEED + 1)))
+                     *learner_alone(learner(), a.envs, a.eval_steps, SEED + 1)))
+    if device_fit:
+        policy.close()
     env.close()
-    print(f"{a.envs} envs; {a.steps} steps per rollout; {a.fit_steps} Adam steps per fit; learner alone: {a.eval_steps} steps")
+    print(f"{a.envs} envs; {a.steps} steps per rollout; {a.fit_steps} Adam steps per fit ({a.fit}); learner alone: {a.eval_steps} steps")
     print(f"expert alone over {a.steps} steps: {expert[0]} successes, {expert[1]} placed of {expert[2]} episodes ended")
     print("| stage | beta | pairs | last loss | expert acted | learner alone: successes | placed | episodes ended | success rate |")
     print("|---|---|---|---|---|---|---|---|---|")
