@@ -1215,16 +1215,33 @@ int mmx_policy_set_weights(mmx_policy* p, const float* const* weight_host, const
   return MMX_OK;
 }
 
+// What mmx_rollout_policy and mmx_rollout_dagger ask of their arguments, in this order, each refusal with the
+// caller's own text: `args_ok` (the caller's NULL and count test, which may not touch sim or policy unless both are
+// given), the sim's action mode where the rollout needs one (`mode` >= 0), the policy's action width, the policy's
+// device.  On MMX_OK *P holds the policy's parameters with the call counter of this rollout filled in.
+struct PolicyRolloutTexts { const char *args, *mode, *width, *device; };
+static int policy_rollout_args(mmx_sim* sim, const mmx_policy* policy, bool args_ok, int mode, int width, uint64_t call,
+                               const PolicyRolloutTexts& text, MmxPolicy* P) {
+  if (!sim || !policy || !args_ok) return sim ? fail(sim, MMX_EINVAL, text.args) : MMX_EINVAL;
+  if (mode >= 0 && sim->S.action_mode != mode) return fail(sim, MMX_EINVAL, text.mode);
+  if (policy->P.A != (width ? width : kDim[sim->S.action_mode])) return fail(sim, MMX_EINVAL, text.width);
+  if (policy->device != sim->cfg.device) return fail(sim, MMX_EINVAL, text.device);
+  *P = policy->P;
+  P->call_lo = (uint32_t)call, P->call_hi = (uint32_t)(call >> 32);
+  return MMX_OK;
+}
+
 int mmx_rollout_policy(mmx_sim* sim, mmx_policy* policy, int32_t n_env_steps, uint64_t call, const mmx_policy_record* prec,
                        const mmx_trajectory* rec) {
-  if (!sim || !policy || !prec || !prec->actions || n_env_steps < 0)
-    return sim ? fail(sim, MMX_EINVAL, "mmx_rollout_policy: bad arguments (NULL policy or actions, or n_env_steps < 0)") : MMX_EINVAL;
-  if (policy->P.A != kDim[sim->S.action_mode])
-    return fail(sim, MMX_EINVAL, "mmx_rollout_policy: the policy's action width is not the sim's action dimension");
-  if (policy->device != sim->cfg.device) return fail(sim, MMX_EINVAL, "mmx_rollout_policy: the policy was created on another device");
+  MmxPolicy P;
+  const int rc = policy_rollout_args(  // (width 0: the sim's action dimension)
+      sim, policy, prec && prec->actions && n_env_steps >= 0, -1, 0, call,
+      {"mmx_rollout_policy: bad arguments (NULL policy or actions, or n_env_steps < 0)", nullptr,
+       "mmx_rollout_policy: the policy's action width is not the sim's action dimension",
+       "mmx_rollout_policy: the policy was created on another device"},
+      &P);
+  if (rc != MMX_OK) return rc;
   const MMXTraj R = traj_arg(rec);
-  MmxPolicy P = policy->P;
-  P.call_lo = (uint32_t)call, P.call_hi = (uint32_t)(call >> 32);
   const MMXPolicyRec PR{prec->actions, prec->mean, prec->noise};
   const auto launch = step_launchers(sim).policy;
   return rollout(sim, n_env_steps, "mmx_rollout_policy", false,
@@ -1237,19 +1254,19 @@ int mmx_rollout_policy(mmx_sim* sim, mmx_policy* policy, int32_t n_env_steps, ui
 // with the FSM expert planning beside the learner and a gate choosing who acts
 int mmx_rollout_dagger(mmx_sim* sim, mmx_policy* policy, int32_t n_env_steps, uint64_t call, const mmx_dagger_config* cfg,
                        const mmx_dagger_record* drec, const mmx_trajectory* rec) {
-  if (!sim || !policy || !cfg || !drec || !drec->actions || n_env_steps < 0)
-    return sim ? fail(sim, MMX_EINVAL, "mmx_rollout_dagger: bad arguments (NULL policy, cfg, drec or actions, or n_env_steps < 0)")
-               : MMX_EINVAL;
-  if (sim->S.action_mode != MMX_ACTION_ABS_POS) return fail(sim, MMX_EINVAL, "mmx_rollout_dagger needs action_mode abs_pos");
-  if (policy->P.A != 4) return fail(sim, MMX_EINVAL, "mmx_rollout_dagger: the policy's action width is not 4");
-  if (policy->device != sim->cfg.device) return fail(sim, MMX_EINVAL, "mmx_rollout_dagger: the policy was created on another device");
+  MmxPolicy P;
+  const int rc = policy_rollout_args(
+      sim, policy, cfg && drec && drec->actions && n_env_steps >= 0, MMX_ACTION_ABS_POS, 4, call,
+      {"mmx_rollout_dagger: bad arguments (NULL policy, cfg, drec or actions, or n_env_steps < 0)",
+       "mmx_rollout_dagger needs action_mode abs_pos", "mmx_rollout_dagger: the policy's action width is not 4",
+       "mmx_rollout_dagger: the policy was created on another device"},
+      &P);
+  if (rc != MMX_OK) return rc;
   // (written so that a NaN fails every test)
   if (!(cfg->beta >= 0.f && cfg->beta <= 1.f)) return fail(sim, MMX_EINVAL, "mmx_rollout_dagger: beta outside [0, 1]");
   if (!(cfg->takeover_dist >= 0.f && cfg->takeover_dist <= FLT_MAX))
     return fail(sim, MMX_EINVAL, "mmx_rollout_dagger: takeover_dist negative or not finite");
   const MMXTraj R = traj_arg(rec);
-  MmxPolicy P = policy->P;
-  P.call_lo = (uint32_t)call, P.call_hi = (uint32_t)(call >> 32);
   // the learner's row: the caller's policy_action, or the actions array itself (read back before it is overwritten)
   float* const learner = drec->policy_action ? drec->policy_action : drec->actions;
   const MMXPolicyRec PR{learner, drec->mean, drec->noise};

@@ -35,8 +35,9 @@
 //   mmx_step_solver.inc       the Newton solver (LANE is the opaque lane id inside it)
 //   mmx_step_integrate.inc    implicitfast + advance, the IK, mj_step_wave and its barrier table
 //   mmx_step_task.inc         numpy's PCG64, the task layer, record I/O
-//   mmx_step_kernels.inc      step_end, substep / step_begin / step_finish, the helper wave's loop, the kernels,
-//                             the launchers
+//   mmx_step_kernels.inc      step_end, substep / step_begin / step_finish, the fused step loop -- stated there once
+//                             per wave (MMX_ENV_WAVE_STEPS, MMX_HELPER_WAVE_STEPS) with the kernel entry
+//                             (MMX_STEP_KERNEL_ENTRY); the five fused kernels only add to it -- the kernels, the launchers
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

@@ -1,6 +1,7 @@
 // Part 8 of mmx_step.inc, its last (an ordered fragment, included there and nowhere else): the end of an env
-// step (step_end), the out-of-line substep / step_begin / step_finish, the profile build's stamps, the helper
-// wave's loop (MMX_HELPER_WAVE_STEPS), the five fused step kernels and the one-substep kernel, and their
+// step (step_end), the out-of-line substep / step_begin / step_finish, the profile build's stamps, the fused
+// step loop, stated once per wave (MMX_ENV_WAVE_STEPS, MMX_HELPER_WAVE_STEPS) with the kernel entry
+// (MMX_STEP_KERNEL_ENTRY), the five fused step kernels built from them and the one-substep kernel, and their
 // launchers.  Relies on every part before it: the record g_E and the scratch map (lds), kinematics_wave /
 // dynamics_wave (dynamics), the collide_* passes (collision), ik_wave and mj_step_wave (integrate), EPI / EPF,
 // the task layer and load_env / store_env / store_obs (task), on mmx_policy.h for policy_act and on mmx_dagger.h
@@ -117,12 +118,16 @@ __device__ __attribute__((noinline)) void substep(int max_iter, float tol, float
   mj_step_wave(max_iter, tol, E, con_dst);
 }
 
-// The whole PickPlaceGymEnv.step in ONE launch (product path): the 16 substeps loop inside the
-// workgroup, so per-env cost variation averages out over the step instead of stretching 16
-// separate launch tails (measured: one launch per substep ran 40 % slower).  With the on-device
-// FSM expert (expert = 1) a launch may also run `nsteps` consecutive env steps of its env: each
-// iteration is exactly one launch's body (record loaded, stepped, stored), so the trajectory is
-// bit-identical to nsteps single-step launches, minus nsteps - 1 launch tails.
+// Lane 0 takes the env step's action (step_begin, and mmx_substep_kernel's first launch of a gym step): the FSM
+// expert's plan(16) or the env's row of `action`, into the scratch slot SCR_ACT (E.J is free before the
+// substeps), then the decode into the record's target.
+DEV void take_action_lane0(const MMXState& S, int i, EnvSh& E, const float* action, int adim, int expert) {
+  float* act = scr_of(E) + SCR_ACT;
+  if (expert) expert_plan(S, i, obj_pos(E, EPI(EPI_OBJ)), hand_pos(E), MMX_NSUBSTEP, act);
+  else
+    for (int k = 0; k < adim && k < 12; k++) act[k] = action[(size_t)i * adim + k];
+  decode_lane0(S, i, E, act);
+}
 // The step's prologue (record load, FSM plan, action decode) and epilogue (position stage, reward,
 // observation, autoreset, record store) are out of line like the substep: inlined into the fused
 // step loop they kept ~280 VGPRs of hoisted values live across iterations (scratch spills).  Like
@@ -130,14 +135,8 @@ __device__ __attribute__((noinline)) void substep(int max_iter, float tol, float
 __device__ __attribute__((noinline)) void step_begin(const MMXState& S, int i, const float* action, int adim,
                                                      int expert) {
   EnvSh& E = g_E;
-  float* act = scr_of(E) + SCR_ACT;  // lane 0's decoded action (E.J is free before the substeps)
   load_env(S, i, E);
-  if (LANE == 0) {
-    if (expert) expert_plan(S, i, obj_pos(E, EPI(EPI_OBJ)), hand_pos(E), MMX_NSUBSTEP, act);
-    else
-      for (int k = 0; k < adim && k < 12; k++) act[k] = action[(size_t)i * adim + k];
-    decode_lane0(S, i, E, act);
-  }
+  if (LANE == 0) take_action_lane0(S, i, E, action, adim, expert);
   SYNC();
 }
 __device__ __attribute__((noinline)) void step_finish(const MMXState& S, int i) {
@@ -191,6 +190,11 @@ static __device__ double g_fsm_prof[11 * FSMP_N];
 #define FSMP_SUBSTEPS_END
 #define FSMP_STEP_END
 #endif
+// (the stamps of a kernel without a per-phase profile, in every build: MMX_ENV_WAVE_STEPS's `stamps` argument)
+#define NOFSMP_STEP_START
+#define NOFSMP_SUBSTEPS_START
+#define NOFSMP_SUBSTEPS_END
+#define NOFSMP_STEP_END
 
 // waves per SIMD the step kernel's register allocation is made for: 3 for the 128-row layout (168
 // VGPRs: twelve envs per CU); 2 for the 192-row layout, the one for batches that leave CU slots empty
@@ -215,15 +219,15 @@ static __device__ double g_fsm_prof[11 * FSMP_N];
 
 #if MMX_STEP_HELPER
 // The helper wave's side of `nsteps` env steps of a fused step kernel (192 rows: threads 64..127), stated once
-// for mmx_env_step_kernel, mmx_env_traj_kernel, mmx_env_policy_kernel and mmx_env_dagger_kernel, which use it
-// inside their `if (threadIdx.x >= 64) { ...; return; }`.  It crosses exactly the workgroup barriers of the env wave's step
-// loop, no path of either wave skipping one: between two steps the fence and the barrier behind the record
-// stores, then the barrier after step_begin's record load, then per substep C, K, A, P, Q, the table in
+// for mmx_env_step_kernel, mmx_env_traj_kernel, mmx_env_policy_kernel and mmx_env_dagger_kernel, which take it
+// through their entry (MMX_STEP_KERNEL_ENTRY).  It crosses exactly the workgroup barriers of the env wave's step
+// loop (MMX_ENV_WAVE_STEPS), no path of either wave skipping one: between two steps the fence and the barrier
+// behind the record stores, then the barrier after step_begin's record load, then per substep C, K, A, P, Q, the table in
 // mj_step_wave (mmx_step_integrate.inc), with the helper's work between them: the IK in C..K, the dynamics in
 // A..P, the GJK / EPA pairs in P..Q.  What a kernel's env wave adds around step_begin and step_finish --
-// policy_act before, traj_record after, dagger_begin in step_begin's place -- holds no workgroup barrier, so the helper has nothing to mirror
-// for it: it waits at the record-load barrier meanwhile.  mmx_substep_kernel follows the same sequence for
-// its one substep.
+// policy_act before, traj_record after, dagger_begin in step_begin's place -- holds no workgroup barrier, so the
+// helper has nothing to mirror for it: it waits at the record-load barrier meanwhile.  mmx_substep_kernel
+// follows the same sequence for its one substep.
 // A macro, not a function: the loop as one force-inlined DEV function keeps every instruction count and still
 // changes the register allocation of all three 192-row kernels (tried twice, and once more when this macro was
 // written: the listings first differ in a v_cndmask_b32_e64 v64 that becomes v7), while these tokens pasted
@@ -244,34 +248,63 @@ static __device__ double g_fsm_prof[11 * FSMP_N];
       __syncthreads();                                     /* Q */                                           \
     }                                                                                                        \
   }
+#define MMX_HELPER_WAVE_BRANCH                                                                               \
+  if (threadIdx.x >= 64) { /* the helper wave: the same workgroup barriers as the env's wave */              \
+    MMX_HELPER_WAVE_STEPS(nsteps)                                                                            \
+    return;                                                                                                  \
+  }
+#else
+#define MMX_HELPER_WAVE_BRANCH
 #endif
 
+// The env wave's side of the same loop, stated once for all five fused kernels: env steps k = 0 .. nsteps - 1 of
+// env i of S.  What the loop guarantees, whatever a kernel hangs on it:
+//  - each iteration is exactly one single-step launch's body -- the record loaded (`begin`: step_begin, or
+//    dagger_begin in its place, behind whatever computes the action), the 16 out-of-line substeps, the record and
+//    the outputs stored (step_finish) -- and between two iterations the previous step's record and observation
+//    stores complete before the next one reads them (the seam: fence and workgroup barrier).  So a fused launch
+//    is bit for bit the same number of single-step launches, however the steps fall into launches;
+//  - the workgroup barriers are the seam's, the record-load barrier behind `begin` and those of the substeps, and
+//    no others: `begin` and `after` are a kernel's own statements (they may use k, and what `begin` declares is
+//    in scope for `after`) and must hold NO workgroup barrier, because the helper wave of the 192-row layout
+//    crosses exactly the barriers stated here (MMX_HELPER_WAVE_STEPS) and a barrier on one side only hangs it.
+// `nsteps` is read again at every test, so `after` may raise it (the budgeted kernel's open-ended count).
+// `stamps` is FSMP for the profile build's per-phase stamps around the step and its substeps, NOFSMP for none.
+// A macro for the reason given at MMX_HELPER_WAVE_STEPS: pasted tokens leave the five kernels' listings what the
+// written-out copies gave (tools/isa_same.py, profiles/r22_isa_same.json).  Do not convert it.
+#define MMX_ENV_WAVE_STEPS(nsteps, stamps, begin, after)                                                     \
+  for (int k = 0; k < (nsteps); k++) {                                                                       \
+    if (k) { /* the seam */                                                                                  \
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");                                                 \
+      XSYNC();                                                                                               \
+    }                                                                                                        \
+    stamps##_STEP_START;                                                                                     \
+    begin;                                                                                                   \
+    XSYNC(); /* the record load */                                                                           \
+    stamps##_SUBSTEPS_START                                                                                  \
+    for (int sub = 0; sub < MMX_NSUBSTEP; sub++)                                                             \
+      substep(S.solver_max_iter, S.solver_tol, sub == MMX_NSUBSTEP - 1 ? contacts_dst(S, i) : nullptr);      \
+    stamps##_SUBSTEPS_END                                                                                    \
+    step_finish(S, i);                                                                                       \
+    stamps##_STEP_END                                                                                        \
+    after;                                                                                                   \
+  }
+// A fused kernel's entry, from its arguments S, base, order and (192 rows) nsteps: the env index i -- order
+// (optional) lists the launch's envs in dispatch order, the grasp-carrying ones first (mmx_order_kernel) -- the
+// bounds test, and the helper wave's whole part in the kernel.
+#define MMX_STEP_KERNEL_ENTRY                                  \
+  const int i = order ? order[blockIdx.x] : base + blockIdx.x; \
+  if (i >= S.N) return;                                        \
+  MMX_HELPER_WAVE_BRANCH
+
+// The whole PickPlaceGymEnv.step in ONE launch (product path): the 16 substeps loop inside the workgroup, so
+// per-env cost variation averages out over the step instead of stretching 16 separate launch tails (measured:
+// one launch per substep ran 40 % slower).  With the on-device FSM expert (expert = 1) a launch may also run
+// `nsteps` consecutive env steps of its env, minus nsteps - 1 launch tails.  The per-phase profile's kernel.
 MMX_STEP_KERNEL MMX_STEP_SYM(mmx_env_step_kernel)(MMXState S, const float* action, int adim, int expert, int base, int nsteps,
                                                   const int* order) {
-  // order (optional): the launch's envs in dispatch order, the grasp-carrying ones first (mmx_order_kernel)
-  const int i = order ? order[blockIdx.x] : base + blockIdx.x;
-  if (i >= S.N) return;
-#if MMX_STEP_HELPER
-  if (threadIdx.x >= 64) {  // the helper wave: the same workgroup barriers as the env's wave below
-    MMX_HELPER_WAVE_STEPS(nsteps)
-    return;
-  }
-#endif
-  for (int k = 0; k < nsteps; k++) {
-    if (k) {  // the previous step's record stores complete before this step reloads it
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-      XSYNC();
-    }
-    FSMP_STEP_START;
-    step_begin(S, i, action, adim, expert);
-    XSYNC();
-    FSMP_SUBSTEPS_START
-    for (int sub = 0; sub < MMX_NSUBSTEP; sub++)
-      substep(S.solver_max_iter, S.solver_tol, sub == MMX_NSUBSTEP - 1 ? contacts_dst(S, i) : nullptr);
-    FSMP_SUBSTEPS_END
-    step_finish(S, i);
-    FSMP_STEP_END
-  }
+  MMX_STEP_KERNEL_ENTRY
+  MMX_ENV_WAVE_STEPS(nsteps, FSMP, step_begin(S, i, action, adim, expert), )
 }
 
 #if !MMX_STEP_HELPER
@@ -290,15 +323,13 @@ DEV unsigned long long budget_now(int k, int i) {
 // 1.45 M to 2.5 M cycles a step by FSM phase, so after equal counts they end milliseconds apart and the
 // slots of the early ones stay empty until the lane's next launch; after equal times they end within a step
 // of each other, the cheap envs a few steps ahead of the plan and the dear ones behind it, every env
-// inside [lo, hi].  Each iteration is one single-step launch's body, as above, so the trajectories are
-// bit-identical however the steps fall into launches.  The test is made once per env step, after
-// step_finish, from scalar values (the count, the bounds, the clock), so it is the same for the whole wave;
+// inside [lo, hi].  The test is made once per env step, after step_finish, from scalar values (the count, the
+// bounds, the clock), so it is the same for the whole wave;
 // lane 0 then writes the env's count back and adds the workgroup's steps and ticks to the launch's sums, from
 // which the lane's next launch (same stream: ordered after this one) takes its ticks per step.
 MMX_STEP_KERNEL mmx_env_step_budget_kernel(MMXState S, MMXBudget B, const float* action, int adim, int base,
                                            const int* order) {
-  const int i = order ? order[blockIdx.x] : base + blockIdx.x;
-  if (i >= S.N) return;
+  MMX_STEP_KERNEL_ENTRY
   const int first = __builtin_amdgcn_readfirstlane(B.done[i]);
   const unsigned long long t0 = budget_now(0, i);
   unsigned long long budget = 0;
@@ -312,26 +343,11 @@ MMX_STEP_KERNEL mmx_env_step_budget_kernel(MMXState S, MMXBudget B, const float*
     const unsigned long long steps = last[0], ticks = last[1];
     if (steps) budget = (unsigned long long)((float)B.nominal * ((float)ticks / (float)steps));
   }
-  // the step loop of mmx_env_step_kernel, its count open at the end: at least up to lo, then a step at a time
-  // while the clock and hi allow
+  // the count is open at the end: at least up to lo, then a step at a time while the clock and hi allow
   const int most = B.hi - first;
   int nsteps = max(B.lo - first, most > 0 && budget > 0 ? 1 : 0);
-  for (int k = 0; k < nsteps; k++) {
-    if (k) {  // the previous step's record stores complete before this step reloads it
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-      XSYNC();
-    }
-    FSMP_STEP_START;
-    step_begin(S, i, action, adim, 1);
-    XSYNC();
-    FSMP_SUBSTEPS_START
-    for (int sub = 0; sub < MMX_NSUBSTEP; sub++)
-      substep(S.solver_max_iter, S.solver_tol, sub == MMX_NSUBSTEP - 1 ? contacts_dst(S, i) : nullptr);
-    FSMP_SUBSTEPS_END
-    step_finish(S, i);
-    FSMP_STEP_END
-    if (k + 1 == nsteps) nsteps += __builtin_amdgcn_readfirstlane(nsteps < most && budget_now(nsteps, i) - t0 < budget);
-  }
+  MMX_ENV_WAVE_STEPS(nsteps, FSMP, step_begin(S, i, action, adim, 1),
+                     if (k + 1 == nsteps) nsteps += __builtin_amdgcn_readfirstlane(nsteps < most && budget_now(nsteps, i) - t0 < budget))
   if (LANE == 0) {
     B.done[i] = first + nsteps;
     if (B.log) B.log[i] = first + nsteps;
@@ -370,31 +386,15 @@ DEV void traj_record(const MMXState& S, const MMXTraj& R, int i, size_t row) {
 // mmx_env_step_kernel's step loop with an action row per step and a per-step record (mmx_rollout_actions,
 // mmx_rollout_expert_record): step k of the launch is the rollout's step k0 + k; it reads the actions
 // [T][N][adim] at row k0 + k (expert = 1: planned in the kernel, as above) and, after step_finish, writes
-// the env's outputs to slice k0 + k of the arrays of R.  Each iteration is one single-step launch's body,
-// so states and records are bit-identical to a loop of mmx_step calls.  No per-phase profile here.
+// the env's outputs to slice k0 + k of the arrays of R: states and records are bit-identical to a loop of
+// mmx_step calls.  No per-phase profile here.
 MMX_STEP_KERNEL MMX_STEP_SYM(mmx_env_traj_kernel)(MMXState S, MMXTraj R, const float* actions, int adim, int expert, int base,
                                                   int nsteps, int k0, const int* order) {
-  const int i = order ? order[blockIdx.x] : base + blockIdx.x;
-  if (i >= S.N) return;
-#if MMX_STEP_HELPER
-  if (threadIdx.x >= 64) {  // the helper wave
-    MMX_HELPER_WAVE_STEPS(nsteps)
-    return;
-  }
-#endif
-  for (int k = 0; k < nsteps; k++) {
-    if (k) {  // the previous step's record stores complete before this step reloads it
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-      XSYNC();
-    }
-    const size_t step = (size_t)(k0 + k);
-    step_begin(S, i, expert ? actions : actions + step * (size_t)S.N * (size_t)adim, adim, expert);
-    XSYNC();
-    for (int sub = 0; sub < MMX_NSUBSTEP; sub++)
-      substep(S.solver_max_iter, S.solver_tol, sub == MMX_NSUBSTEP - 1 ? contacts_dst(S, i) : nullptr);
-    step_finish(S, i);
-    traj_record(S, R, i, step * (size_t)S.N + (size_t)i);
-  }
+  MMX_STEP_KERNEL_ENTRY
+  MMX_ENV_WAVE_STEPS(nsteps, NOFSMP,
+                     const size_t step = (size_t)(k0 + k);
+                     step_begin(S, i, expert ? actions : actions + step * (size_t)S.N * (size_t)adim, adim, expert),
+                     traj_record(S, R, i, step * (size_t)S.N + (size_t)i))
 }
 
 // The policy's action for the env step that follows (mmx_env_policy_kernel), on the env's wave, out of line like
@@ -453,28 +453,12 @@ MMX_DEFINE_POLICY_ACT(dagger_policy_act)
 // kernel's body, so states and records are bit for bit what mmx_rollout_actions gives on the recorded actions.
 MMX_STEP_KERNEL MMX_STEP_SYM(mmx_env_policy_kernel)(MMXState S, MMXTraj R, MmxPolicy P, MMXPolicyRec PR, int base, int nsteps,
                                                     int k0, const int* order) {
-  const int i = order ? order[blockIdx.x] : base + blockIdx.x;
-  if (i >= S.N) return;
-#if MMX_STEP_HELPER
-  if (threadIdx.x >= 64) {  // the helper wave (the env wave runs the policy before step_begin's record load)
-    MMX_HELPER_WAVE_STEPS(nsteps)
-    return;
-  }
-#endif
-  for (int k = 0; k < nsteps; k++) {
-    if (k) {  // the previous step's record and observation stores complete before this step reads them
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-      XSYNC();
-    }
-    const size_t step = (size_t)(k0 + k);
-    policy_act(S, P, PR, i, (unsigned)step);
-    step_begin(S, i, PR.actions + step * (size_t)S.N * (size_t)P.A, P.A, 0);
-    XSYNC();
-    for (int sub = 0; sub < MMX_NSUBSTEP; sub++)
-      substep(S.solver_max_iter, S.solver_tol, sub == MMX_NSUBSTEP - 1 ? contacts_dst(S, i) : nullptr);
-    step_finish(S, i);
-    traj_record(S, R, i, step * (size_t)S.N + (size_t)i);
-  }
+  MMX_STEP_KERNEL_ENTRY
+  MMX_ENV_WAVE_STEPS(nsteps, NOFSMP,
+                     const size_t step = (size_t)(k0 + k);
+                     policy_act(S, P, PR, i, (unsigned)step);
+                     step_begin(S, i, PR.actions + step * (size_t)S.N * (size_t)P.A, P.A, 0),
+                     traj_record(S, R, i, step * (size_t)S.N + (size_t)i))
 }
 
 // step_begin for a DAgger step (mmx_env_dagger_kernel), out of line and without register saves like it: the
@@ -518,28 +502,12 @@ __device__ __attribute__((noinline)) void dagger_begin(const MMXState& S, const 
 // mmx_expert_plan(16) -> mmx_step(D.actions[t]) gives.
 MMX_STEP_KERNEL MMX_STEP_SYM(mmx_env_dagger_kernel)(MMXState S, MMXTraj R, MmxPolicy P, MMXPolicyRec PR, MMXDagger D, int base,
                                                     int nsteps, int k0, const int* order) {
-  const int i = order ? order[blockIdx.x] : base + blockIdx.x;
-  if (i >= S.N) return;
-#if MMX_STEP_HELPER
-  if (threadIdx.x >= 64) {  // the helper wave (the env wave runs the policy and the gate before the record-load barrier)
-    MMX_HELPER_WAVE_STEPS(nsteps)
-    return;
-  }
-#endif
-  for (int k = 0; k < nsteps; k++) {
-    if (k) {  // the previous step's record and observation stores complete before this step reads them
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-      XSYNC();
-    }
-    const size_t step = (size_t)(k0 + k);
-    dagger_policy_act(S, P, PR, i, (unsigned)step);
-    dagger_begin(S, P, D, i, (unsigned)step);
-    XSYNC();
-    for (int sub = 0; sub < MMX_NSUBSTEP; sub++)
-      substep(S.solver_max_iter, S.solver_tol, sub == MMX_NSUBSTEP - 1 ? contacts_dst(S, i) : nullptr);
-    step_finish(S, i);
-    traj_record(S, R, i, step * (size_t)S.N + (size_t)i);
-  }
+  MMX_STEP_KERNEL_ENTRY
+  MMX_ENV_WAVE_STEPS(nsteps, NOFSMP,
+                     const size_t step = (size_t)(k0 + k);
+                     dagger_policy_act(S, P, PR, i, (unsigned)step);
+                     dagger_begin(S, P, D, i, (unsigned)step),
+                     traj_record(S, R, i, step * (size_t)S.N + (size_t)i))
 }
 
 // One IK + mj_step substep per launch (mmx_launch_physics, the physics-level harness of mmx_physics_step;
@@ -551,7 +519,6 @@ MMX_STEP_KERNEL MMX_STEP_SYM(mmx_env_dagger_kernel)(MMXState S, MMXTraj R, MmxPo
 extern "C" __global__ void __launch_bounds__(MMX_STEP_THREADS) MMX_STEP_SYM(mmx_substep_kernel)(MMXState S, const float* action,
                                                                                             int adim, int mode) {
   EnvSh& E = g_E;
-  float* act = scr_of(E) + SCR_ACT;  // lane 0's decoded action (E.J is free before the substeps)
   const int i = blockIdx.x;
   if (i >= S.N) return;
 #if MMX_STEP_HELPER
@@ -569,12 +536,7 @@ extern "C" __global__ void __launch_bounds__(MMX_STEP_THREADS) MMX_STEP_SYM(mmx_
   }
 #endif
   load_env(S, i, E);
-  if ((mode & SS_FIRST) && (mode & SS_GYM) && LANE == 0) {
-    if (mode & SS_EXPERT) expert_plan(S, i, obj_pos(E, EPI(EPI_OBJ)), hand_pos(E), MMX_NSUBSTEP, act);
-    else
-      for (int k = 0; k < adim && k < 12; k++) act[k] = action[(size_t)i * adim + k];
-    decode_lane0(S, i, E, act);
-  }
+  if ((mode & SS_FIRST) && (mode & SS_GYM) && LANE == 0) take_action_lane0(S, i, E, action, adim, mode & SS_EXPERT);
   SYNC();
 #if MMX_STEP_HELPER
   XSYNC();  // the record and the decoded target are in LDS (the helper's IK and dynamics read them)
@@ -613,14 +575,18 @@ static size_t step_lds_pad() {
   }();
   return pad;
 }
+// The fused kernels' launch line: one workgroup per env of the launch, `count` of them, on the stream `st`.
+template <typename... Params, typename... Args>
+static hipError_t launch_fused(void (*kernel)(Params...), int count, hipStream_t st, const Args&... args) {
+  hipLaunchKernelGGL(kernel, dim3(count), dim3(MMX_STEP_THREADS), step_lds_pad(), st, args...);
+  return hipGetLastError();
+}
 // envs [base, base+count): independent env ranges may run on separate streams
 extern "C" hipError_t MMX_STEP_SYM(mmx_launch_step)(const MMXState* S, const float* action, int adim, int expert, int base,
                                                     int count, int nsteps, hipStream_t st, const int* order) {
   if (count <= 0 || nsteps <= 0) return hipSuccess;
   if (nsteps > 1 && !expert) return hipErrorInvalidValue;  // host actions: one env step per launch
-  hipLaunchKernelGGL(MMX_STEP_SYM(mmx_env_step_kernel), dim3(count), dim3(MMX_STEP_THREADS), step_lds_pad(), st, *S, action, adim, expert, base,
-                     nsteps, order);
-  return hipGetLastError();
+  return launch_fused(MMX_STEP_SYM(mmx_env_step_kernel), count, st, *S, action, adim, expert, base, nsteps, order);
 }
 #if !MMX_STEP_HELPER
 // expert steps of envs [base, base+count) up to the bounds and the budget of B (the one-wave layout only)
@@ -628,9 +594,7 @@ extern "C" hipError_t mmx_launch_step_budget(const MMXState* S, const MMXBudget*
                                              int count, hipStream_t st, const int* order) {
   if (count <= 0) return hipSuccess;
   if (!B->done || !B->acc || B->round < 0 || B->lo < 0 || B->lo > B->hi) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(mmx_env_step_budget_kernel, dim3(count), dim3(MMX_STEP_THREADS), step_lds_pad(), st, *S, *B, action, adim,
-                     base, order);
-  return hipGetLastError();
+  return launch_fused(mmx_env_step_budget_kernel, count, st, *S, *B, action, adim, base, order);
 }
 #endif
 // n substeps of every env, one launch each (mmx_physics_step)
@@ -646,9 +610,7 @@ extern "C" hipError_t MMX_STEP_SYM(mmx_launch_traj)(const MMXState* S, const MMX
                                                     int expert, int base, int count, int nsteps, int k0, hipStream_t st,
                                                     const int* order) {
   if (count <= 0 || nsteps <= 0) return hipSuccess;
-  hipLaunchKernelGGL(MMX_STEP_SYM(mmx_env_traj_kernel), dim3(count), dim3(MMX_STEP_THREADS), step_lds_pad(), st, *S, *R, actions, adim,
-                     expert, base, nsteps, k0, order);
-  return hipGetLastError();
+  return launch_fused(MMX_STEP_SYM(mmx_env_traj_kernel), count, st, *S, *R, actions, adim, expert, base, nsteps, k0, order);
 }
 // `nsteps` env steps of envs [base, base+count) from the rollout's step k0 on, every action from the policy P
 extern "C" hipError_t MMX_STEP_SYM(mmx_launch_policy)(const MMXState* S, const MMXTraj* R, const MmxPolicy* P,
@@ -656,9 +618,7 @@ extern "C" hipError_t MMX_STEP_SYM(mmx_launch_policy)(const MMXState* S, const M
                                                       hipStream_t st, const int* order) {
   if (count <= 0 || nsteps <= 0) return hipSuccess;
   if (!PR->actions || !P->data) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(MMX_STEP_SYM(mmx_env_policy_kernel), dim3(count), dim3(MMX_STEP_THREADS), step_lds_pad(), st, *S, *R, *P, *PR,
-                     base, nsteps, k0, order);
-  return hipGetLastError();
+  return launch_fused(MMX_STEP_SYM(mmx_env_policy_kernel), count, st, *S, *R, *P, *PR, base, nsteps, k0, order);
 }
 // `nsteps` DAgger env steps of envs [base, base+count) from the rollout's step k0 on: the policy P acts or the FSM
 // expert does, by the gate of D; PR->actions is the learner's row and must be D->policy_action (a four-wide policy)
@@ -667,7 +627,5 @@ extern "C" hipError_t MMX_STEP_SYM(mmx_launch_dagger)(const MMXState* S, const M
                                                       int nsteps, int k0, hipStream_t st, const int* order) {
   if (count <= 0 || nsteps <= 0) return hipSuccess;
   if (!D->actions || !D->policy_action || PR->actions != D->policy_action || !P->data || P->A != 4) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(MMX_STEP_SYM(mmx_env_dagger_kernel), dim3(count), dim3(MMX_STEP_THREADS), step_lds_pad(), st, *S, *R, *P, *PR,
-                     *D, base, nsteps, k0, order);
-  return hipGetLastError();
+  return launch_fused(MMX_STEP_SYM(mmx_env_dagger_kernel), count, st, *S, *R, *P, *PR, *D, base, nsteps, k0, order);
 }

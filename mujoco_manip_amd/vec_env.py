@@ -159,6 +159,31 @@ class PickPlaceVecEnv:
         """Device-resident FSM rollout (generate_dataset.py:140-196), no host round trips."""
         self.sim.rollout_expert(n_env_steps)
 
+    def _record_tensors(self, record, T: int, tables, always=()) -> dict:
+        """The record of a rollout of T steps: `record` (a name or names) checked against `tables`, pairs of a
+        field table {name: (width, dtype)} and the ctypes record that takes its arrays, then for those names and
+        the missing ones of `always` behind them {name: tensor [T, N, width]} ([T, N] at width 1), each tensor's
+        address stored in its record."""
+        names = (record,) if isinstance(record, str) else tuple(record or ())
+        allowed = tuple(name for fields, _ in tables for name in fields)
+        for name in names:
+            if name not in allowed:
+                raise ValueError(f"record entries must be among {allowed}, got '{name}'")
+        out = {}
+        for name in names + tuple(n for n in always if n not in names):
+            (width, dtype), rec = next((fields[name], rec) for fields, rec in tables if name in fields)
+            shape = (T, self.num_envs, width) if width > 1 else (T, self.num_envs)
+            out[name] = torch.empty(shape, dtype=getattr(torch, dtype), device=self.device)
+            setattr(rec, name, out[name].data_ptr())
+        return out
+
+    def _check_bound(self, policy):
+        """The policy's device side, given that it is bound to this env."""
+        dev = policy.device_policy
+        if policy.action_dim != self.action_dim or policy._env is not self:
+            raise ValueError("the policy must be bound to this env (MlpPolicy.bind(env))")
+        return dev
+
     def rollout(self, actions: torch.Tensor | None = None, n_steps: int | None = None,
                 record=("obs", "reward", "done")) -> dict:
         """T env steps in fused launches with a per-step record, no host round trips.
@@ -169,10 +194,6 @@ class PickPlaceVecEnv:
         reward_components, target, episode_i, qpos, qvel): slice k is what the env's buffer holds after
         step k, bit for bit what the step() loop gives ("obs" flat [T, N, 85]: split_obs; "done"
         int32 [T, N, 3] = terminated, truncated, success).  The env ends in the loop's final state."""
-        names = (record,) if isinstance(record, str) else tuple(record or ())
-        for name in names:
-            if name not in _lib.TRAJ_FIELDS:
-                raise ValueError(f"record entries must be among {tuple(_lib.TRAJ_FIELDS)}, got '{name}'")
         if actions is None:
             if n_steps is None or int(n_steps) < 0:
                 raise ValueError("rollout needs actions [T, N, A] or n_steps >= 0 for the on-device expert")
@@ -184,12 +205,8 @@ class PickPlaceVecEnv:
             if n_steps is not None and int(n_steps) != a.shape[0]:
                 raise ValueError(f"n_steps {n_steps} does not match the {a.shape[0]} action rows")
             T, a = a.shape[0], a.contiguous()
-        out, rec = {}, _lib.MMXTrajectory()
-        for name in names:
-            width, dtype = _lib.TRAJ_FIELDS[name]
-            shape = (T, self.num_envs, width) if width > 1 else (T, self.num_envs)
-            out[name] = torch.empty(shape, dtype=getattr(torch, dtype), device=self.device)
-            setattr(rec, name, out[name].data_ptr())
+        rec = _lib.MMXTrajectory()
+        out = self._record_tensors(record, T, ((_lib.TRAJ_FIELDS, rec),))
         if T == 0:
             return out
         if a is None:
@@ -207,29 +224,14 @@ class PickPlaceVecEnv:
         [T, N, action_dim] (what the envs were stepped with; rollout(actions=...) from the same state replays the
         call bit for bit), and on request "mean" (the network's output) and "noise" (the normal draws; increment
         `call` per call for fresh ones)."""
-        names = (record,) if isinstance(record, str) else tuple(record or ())
-        own = ("actions", "mean", "noise")
-        for name in names:
-            if name not in _lib.TRAJ_FIELDS and name not in own:
-                raise ValueError(f"record entries must be among {tuple(_lib.TRAJ_FIELDS) + own}, got '{name}'")
+        own = {name: (self.action_dim, "float32") for name in ("actions", "mean", "noise")}
         if n_steps is None or int(n_steps) < 0:
             raise ValueError("rollout_policy needs n_steps >= 0")
-        dev = policy.device_policy
-        if policy.action_dim != self.action_dim or policy._env is not self:
-            raise ValueError("the policy must be bound to this env (MlpPolicy.bind(env))")
-        T = int(n_steps)
-        out, rec, prec = {}, _lib.MMXTrajectory(), _lib.MMXPolicyRecord()
-        for name in names:
-            if name in own:
-                continue
-            width, dtype = _lib.TRAJ_FIELDS[name]
-            shape = (T, self.num_envs, width) if width > 1 else (T, self.num_envs)
-            out[name] = torch.empty(shape, dtype=getattr(torch, dtype), device=self.device)
-            setattr(rec, name, out[name].data_ptr())
-        for name in own:
-            if name == "actions" or name in names:
-                out[name] = torch.empty((T, self.num_envs, self.action_dim), dtype=torch.float32, device=self.device)
-                setattr(prec, name, out[name].data_ptr())
+        dev = self._check_bound(policy)
+        T, rec, prec = int(n_steps), _lib.MMXTrajectory(), _lib.MMXPolicyRecord()
+        out = self._record_tensors(record, T, ((_lib.TRAJ_FIELDS, rec), (own, prec)), always=("actions",))
+        # (the policy's own arrays behind the env's, in the order of their record)
+        out = {k: out[k] for k in [n for n in out if n not in own] + [n for n in own if n in out]}
         if T == 0:
             return out
         dev.rollout(self.sim, T, call, prec, rec)
@@ -251,17 +253,11 @@ class PickPlaceVecEnv:
         learner was given: it pairs with the label; dagger.DaggerBuffer aggregates the pairs).  The env ends in the
         state of the loop expert_plan(16) -> step(actions[t]); increment `call` per call for fresh draws."""
         T, beta, takeover_dist, names = check_dagger_args(n_steps, beta, takeover_dist, record)
-        dev = policy.device_policy
-        if policy.action_dim != self.action_dim or policy._env is not self:
-            raise ValueError("the policy must be bound to this env (MlpPolicy.bind(env))")
+        dev = self._check_bound(policy)
         if self._action_mode != "abs_pos":
             raise ValueError("rollout_dagger needs action_mode abs_pos (the FSM expert's actions)")
-        out, rec, drec = {}, _lib.MMXTrajectory(), _lib.MMXDaggerRecord()
-        for name in names + (() if "actions" in names else ("actions",)):
-            width, dtype = _lib.DAGGER_FIELDS[name] if name in _lib.DAGGER_FIELDS else _lib.TRAJ_FIELDS[name]
-            shape = (T, self.num_envs, width) if width > 1 else (T, self.num_envs)
-            out[name] = torch.empty(shape, dtype=getattr(torch, dtype), device=self.device)
-            setattr(drec if name in _lib.DAGGER_FIELDS else rec, name, out[name].data_ptr())
+        rec, drec = _lib.MMXTrajectory(), _lib.MMXDaggerRecord()
+        out = self._record_tensors(names, T, ((_lib.TRAJ_FIELDS, rec), (_lib.DAGGER_FIELDS, drec)), always=("actions",))
         if T == 0:
             return out
         dev.rollout_dagger(self.sim, T, call, _lib.MMXDaggerConfig(beta=beta, takeover_dist=takeover_dist), drec, rec)

@@ -20,6 +20,7 @@ env.expert_plan(16) -> env.sim.step(actions[t]) on a fresh env, every sim-owned 
 8. DaggerBuffer on the device.
 """
 import ctypes as C
+import functools
 import hashlib
 
 import numpy as np
@@ -28,12 +29,13 @@ import pytest
 import dagger_ref
 import mppi_ref
 from policy_ref import U, forward64, make_spec
-import test_traj_rollout as TR
+import rollout_support as RS
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-N_ENVS, N_STEPS = TR.N_ENVS, TR.N_STEPS
+N_ENVS, N_STEPS = 10, 11  # tests/test_traj_rollout.py's given-action case
+make_env = functools.partial(RS.make_env, n=N_ENVS, rows=128, seed=7)
 OWN = ("actions", "expert_action", "policy_action", "mean", "noise", "gate", "obs_in")
 # The takeover threshold of test 5, chosen once from the distances |policy_action - expert_action| (xyz) that run 3
 # (beta = 0, rows 128) recorded on an MI355X, near their median (0.2886); see test_takeover for the split it gives.
@@ -66,12 +68,12 @@ def dagger_run(rows, beta, tau=0.0, steps=N_STEPS, max_episode_steps=4, image_si
     from mujoco_manip_amd.policy import MlpPolicy
 
     spec = policy_spec()
-    env = TR.make_env(rows=rows, image_size=image_size, max_episode_steps=max_episode_steps, lib=lib)
-    start = TR.snapshot(env)
+    env = make_env(rows=rows, image_size=image_size, max_episode_steps=max_episode_steps, lib=lib)
+    start = RS.snapshot(env)
     policy = MlpPolicy(**spec).bind(env)
     facts = {"lanes": env.sim.rollout_lanes, "launches": env.sim.rollout_launches(steps)}
-    rec = TR.to_host(env.rollout_dagger(policy, steps, beta=beta, takeover_dist=tau, record=TR.record_names() + OWN, call=call))
-    final = TR.snapshot(env)
+    rec = RS.to_host(env.rollout_dagger(policy, steps, beta=beta, takeover_dist=tau, record=RS.record_names() + OWN, call=call))
+    final = RS.snapshot(env)
     policy.close()
     env.close()
     run = dict(rec=rec, final=final, obs0=start["obs"], ep0=start["episode_i"][:, 12].copy(), spec=spec, facts=facts)
@@ -87,13 +89,13 @@ def loop_run(run, rows, max_episode_steps=4, image_size=0):
     """The host loop expert_plan(16) -> step(actions[t]) on a fresh env with the run's executed actions -> (the
     snapshot after each step, the labels [T, N, 4]); cached per run."""
     if id(run) not in _LOOPS:
-        env = TR.make_env(rows=rows, image_size=image_size, max_episode_steps=max_episode_steps)
+        env = make_env(rows=rows, image_size=image_size, max_episode_steps=max_episode_steps)
         acts = torch.as_tensor(run["rec"]["actions"], device=env.device)
         snaps, labels = [], []
         for t in range(acts.shape[0]):
             labels.append(env.expert_plan(16).cpu().numpy())
             env.sim.step(acts[t].data_ptr(), 4)
-            snaps.append(TR.snapshot(env))
+            snaps.append(RS.snapshot(env))
         env.close()
         _LOOPS[id(run)] = (run, snaps, np.stack(labels))
     return _LOOPS[id(run)][1:]
@@ -113,8 +115,8 @@ def assert_loop(run, rows, **kw):
 
     snaps, labels = loop_run(run, rows, **kw)
     rec = run["rec"]
-    TR.assert_record({k: rec[k] for k in TR.record_names()}, snaps)
-    TR.assert_final(run["final"], snaps[-1])  # images and seg included, with cameras
+    RS.assert_record({k: rec[k] for k in RS.record_names()}, snaps)
+    RS.assert_final(run["final"], snaps[-1])  # images and seg included, with cameras
     bad = np.argwhere(rec["expert_action"] != labels)
     assert bad.size == 0, f"the label differs first at (step, env, component) = {bad[0].tolist()}"
     fsm = rec["episode_i"][:, :, _lib.EPI["fsm_state"]]
@@ -127,7 +129,7 @@ def assert_loop(run, rows, **kw):
 def test_loop_identity(rows, image_size):
     run = dagger_run(rows, 0.5, image_size=image_size)
     rec = run["rec"]
-    assert set(rec) == set(TR.record_names()) | set(OWN)
+    assert set(rec) == set(RS.record_names()) | set(OWN)
     assert rec["actions"].shape == (N_STEPS, N_ENVS, 4) and rec["gate"].shape == (N_STEPS, N_ENVS) and rec["gate"].dtype == np.int32
     assert rec["obs_in"].shape == (N_STEPS, N_ENVS, 85) and all(np.isfinite(rec[k]).all() for k in OWN if k != "gate")
     if image_size == 0:  # four staggered lanes, several launches each, some of several steps
@@ -149,15 +151,15 @@ def test_beta_one_is_the_expert(rows):
     T = 60
     run = dagger_run(rows, 1.0, steps=T, max_episode_steps=200)
     rec = run["rec"]
-    env = TR.make_env(rows=rows, max_episode_steps=200)
-    want = TR.to_host(env.rollout(n_steps=T, record=TR.record_names()))
-    final = TR.snapshot(env)
+    env = make_env(rows=rows, max_episode_steps=200)
+    want = RS.to_host(env.rollout(n_steps=T, record=RS.record_names()))
+    final = RS.snapshot(env)
     env.close()
-    for name in TR.record_names():
+    for name in RS.record_names():
         assert rec[name].dtype == want[name].dtype and rec[name].shape == want[name].shape, name
         bad = np.argwhere(rec[name] != want[name])
         assert bad.size == 0, f"record '{name}' differs first at (step, env, ...) = {bad[0].tolist()}"
-    TR.assert_final(run["final"], final)
+    RS.assert_final(run["final"], final)
     assert ((rec["gate"] & 1) == 1).all() and (rec["gate"] >> 1 == 0).all()
     assert (rec["actions"].view(np.uint32) == rec["expert_action"].view(np.uint32)).all()
     phases = np.bitwise_or.reduce(rec["episode_i"][:, :, _lib.EPI["fsm_phases"]].ravel())
@@ -257,11 +259,11 @@ def test_refusals():
     from mujoco_manip_amd.policy import MlpPolicy
     from mujoco_manip_amd.vec_env import PickPlaceVecEnv
 
-    env = TR.make_env(n=2)
+    env = make_env(n=2)
     L, sim = env.sim.L, env.sim.ptr
     policy = MlpPolicy(**policy_spec()).bind(env)
     pol = policy.device_policy.ptr
-    before = TR.snapshot(env)
+    before = RS.snapshot(env)
     arrays = {k: torch.full((3, 2, w) if w > 1 else (3, 2), -77, dtype=getattr(torch, t), device=env.device)
               for k, (w, t) in _lib.DAGGER_FIELDS.items()}
     drec = _lib.MMXDaggerRecord(**{k: v.data_ptr() for k, v in arrays.items()})
@@ -281,10 +283,10 @@ def test_refusals():
         assert call(sim, pol, 3, 0, cfg(beta=beta), C.byref(drec), None) == -1, beta
     for tau in (-1e-6, float("nan"), float("inf")):
         assert call(sim, pol, 3, 0, cfg(tau=tau), C.byref(drec), None) == -1, tau
-    rel = TR.make_env(n=2, mode=TR.REL)  # not an abs_pos sim
-    rel_before = TR.snapshot(rel)
+    rel = make_env(n=2, mode=RS.REL)  # not an abs_pos sim
+    rel_before = RS.snapshot(rel)
     assert call(rel.sim.ptr, pol, 3, 0, cfg(), C.byref(drec), None) == -1
-    TR.assert_final(TR.snapshot(rel), rel_before)
+    RS.assert_final(RS.snapshot(rel), rel_before)
     rel.close()
     wide = _lib.Policy(env.sim, [(np.zeros((10, 85), np.float32), None)], 0)  # an action width of 10
     assert call(sim, wide.ptr, 3, 0, cfg(), C.byref(drec), None) == -1
@@ -294,7 +296,7 @@ def test_refusals():
         assert call(far.sim.ptr, pol, 3, 0, cfg(), C.byref(drec), None) == -1
         far.close()
     assert call(sim, pol, 0, 0, cfg(), C.byref(drec), None) == 0  # nothing to do
-    TR.assert_final(TR.snapshot(env), before)  # nothing was launched
+    RS.assert_final(RS.snapshot(env), before)  # nothing was launched
     assert all((v == -77).all() for v in arrays.values())
     # the Python layer
     for kw in ({"beta": 1.5}, {"beta": float("nan")}, {"takeover_dist": -0.1}, {"record": ("obs", "images")}):
@@ -305,13 +307,13 @@ def test_refusals():
     unbound = MlpPolicy(**policy_spec())
     with pytest.raises(RuntimeError, match="not bound"):
         env.rollout_dagger(unbound, 3)
-    other = TR.make_env(n=2)
+    other = make_env(n=2)
     with pytest.raises(ValueError, match="bound to this env"):
         other.rollout_dagger(policy, 3)
     other.close()
-    empty = env.rollout_dagger(policy, 0, record=TR.record_names() + OWN)
-    assert set(empty) == set(TR.record_names()) | set(OWN) and all(v.shape[:2] == (0, 2) for v in empty.values())
-    TR.assert_final(TR.snapshot(env), before)
+    empty = env.rollout_dagger(policy, 0, record=RS.record_names() + OWN)
+    assert set(empty) == set(RS.record_names()) | set(OWN) and all(v.shape[:2] == (0, 2) for v in empty.values())
+    RS.assert_final(RS.snapshot(env), before)
     policy.close()
     env.close()
 
@@ -321,7 +323,7 @@ def test_dagger_buffer():
     from mujoco_manip_amd.dagger import DEFAULT_RECORD, DaggerBuffer
     from mujoco_manip_amd.policy import MlpPolicy
 
-    env = TR.make_env()
+    env = make_env()
     policy = MlpPolicy(**policy_spec()).bind(env)
     a = env.rollout_dagger(policy, 3, beta=0.5, call=0)
     b = env.rollout_dagger(policy, 2, beta=0.25, call=1)

@@ -18,6 +18,7 @@ gate; MMX_FIT_MARGINS=<path> collects them.
 7. every MMX_EINVAL case, with the policy untouched;
 8. the DAgger fit end to end, small."""
 import ctypes as C
+import functools
 import json
 import os
 
@@ -26,12 +27,14 @@ import pytest
 
 import policy_fit_ref as R
 from policy_ref import make_spec
-import test_traj_rollout as TR
+import rollout_support as RS
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 F32 = np.float32
+# tests/test_traj_rollout.py's envs
+make_env = functools.partial(RS.make_env, n=10, rows=128, seed=7)
 MARGINS: dict = {}
 
 
@@ -57,7 +60,7 @@ def envs():
     to an env of its own action width: abs_pos has 4, the relative 6D mode 10)."""
     if not torch.cuda.is_available():
         pytest.skip("needs an MI355X")
-    made = {4: TR.make_env(), 10: TR.make_env(mode=TR.REL)}
+    made = {4: make_env(), 10: make_env(mode=RS.REL)}
     yield made
     for e in made.values():
         e.close()
@@ -188,30 +191,30 @@ def test_in_place_and_ordered(rows):
     _, obs, _ = R.make_case((), 4, "tanh", True, 130, seed=41)
     obs[:, 17] = 0.25
     target = np.random.default_rng(4).uniform(spec["low"], spec["high"], (130, 4)).astype(F32)
-    e1 = TR.make_env(rows=rows)
+    e1 = make_env(rows=rows)
     p1 = bind(spec, e1)
     x = dev(obs, e1)
     p1.fit(x, dev(target, e1), 5, batch=64, lr=1e-2, seed=3)  # no synchronise: eval and the rollout queue behind it
     mean1 = p1.eval(x)
-    rec1 = e1.rollout_policy(p1, 8, record=TR.record_names() + ("mean",))
+    rec1 = e1.rollout_policy(p1, 8, record=RS.record_names() + ("mean",))
     layers = [(W.copy(), b.copy()) for W, b in p1.weights()]
-    rec1, mean1, fin1 = TR.to_host(rec1), mean1.cpu().numpy(), TR.snapshot(e1)
+    rec1, mean1, fin1 = RS.to_host(rec1), mean1.cpu().numpy(), RS.snapshot(e1)
     assert any((W != W0).any() for (W, _), (W0, _) in zip(layers, spec["layers"]))
     p1.load(layers)  # set_weights(get_weights()): no bit of the blob's behaviour changes
     assert (p1.eval(x).cpu().numpy() == mean1).all()
     p1.close()
     e1.close()
-    e2 = TR.make_env(rows=rows)
+    e2 = make_env(rows=rows)
     p2 = bind(dict(spec, layers=layers), e2)
     mean2 = p2.eval(dev(obs, e2)).cpu().numpy()
-    rec2 = TR.to_host(e2.rollout_policy(p2, 8, record=TR.record_names() + ("mean",)))
-    fin2 = TR.snapshot(e2)
+    rec2 = RS.to_host(e2.rollout_policy(p2, 8, record=RS.record_names() + ("mean",)))
+    fin2 = RS.snapshot(e2)
     p2.close()
     e2.close()
     assert (mean1 == mean2).all()
     for name in rec1:
         assert (rec1[name] == rec2[name]).all(), name
-    TR.assert_final(fin1, fin2)
+    RS.assert_final(fin1, fin2)
 
 
 # ------------------------------------------------------------------ 6. invisible otherwise
@@ -220,17 +223,17 @@ def test_export_and_reset_are_invisible(rows):
     spec = dict(rollout_spec(), log_std=np.full(4, np.log(0.05), F32))
     recs, fins = [], []
     for reset in (False, True):
-        e = TR.make_env(rows=rows)
+        e = make_env(rows=rows)
         p = bind(spec, e)
         if reset:
             p.load(p.weights())
-        recs.append(TR.to_host(e.rollout_dagger(p, 8, beta=0.5, call=2)))
-        fins.append(TR.snapshot(e))
+        recs.append(RS.to_host(e.rollout_dagger(p, 8, beta=0.5, call=2)))
+        fins.append(RS.snapshot(e))
         p.close()
         e.close()
     for name in recs[0]:
         assert (recs[0][name] == recs[1][name]).all(), name
-    TR.assert_final(fins[0], fins[1])
+    RS.assert_final(fins[0], fins[1])
 
 
 # ------------------------------------------------------------------ 7. refusals
@@ -277,7 +280,7 @@ def test_einval_touches_nothing(env):
 # ------------------------------------------------------------------ 8. end to end, small
 @pytest.mark.parametrize("rows", [128, 192])
 def test_dagger_fit_end_to_end(rows):
-    e = TR.make_env(n=64, rows=rows, max_episode_steps=50)
+    e = make_env(n=64, rows=rows, max_episode_steps=50)
     spec = rollout_spec()
     p = bind(spec, e)
     rec = e.rollout_dagger(p, 40, beta=1.0, record=("obs_in", "expert_action"))  # the expert acts and labels

@@ -24,6 +24,7 @@ the form damps by |x| e^2x / (1 + e^2x)^2 < 0.5); both activations are 1-Lipschi
 Measured on an MI355X (profiles/r16_policy_margins.json): mmx_policy_eval at most 1.5 % of the bound, the rollout's
 mean 0.004 %, tanh 0.31 ACT_EPS, the noise 2.7e-7 from the restatement (bound 1e-4), a noisy action 0.25 of its bound.
 """
+import functools
 import hashlib
 import json
 import os
@@ -33,12 +34,13 @@ import pytest
 
 import mppi_ref
 from policy_ref import ACT_EPS, U, forward64, make_spec
-import test_traj_rollout as TR
+import rollout_support as RS
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-N_ENVS, N_STEPS, REL = TR.N_ENVS, TR.N_STEPS, TR.REL
+N_ENVS, N_STEPS, SEED, REL = 10, 11, 7, RS.REL  # tests/test_traj_rollout.py's given-action case
+make_env = functools.partial(RS.make_env, n=N_ENVS, rows=128, seed=SEED)
 MARGINS: dict = {}  # name -> the worst fraction of its bound seen in this session
 
 
@@ -89,18 +91,18 @@ def policy_run(rows, mode, stochastic=False, image_size=0, call=0, lib=None):
     key = (rows, mode, stochastic, image_size, call, lib)
     if key in _RUNS:
         return _RUNS[key]
-    A = TR.MODES[mode] if mode == "abs_pos" else 10
+    A = 4 if mode == "abs_pos" else 10
     low, high = mode_box(mode)
     # (spread and gain chosen on the envs' own observations: 15 % and 11 % of the outputs leave the two boxes)
     spec = make_spec(A, low=low, high=high, log_std=np.full(A, np.log(0.05), np.float32) if stochastic else None,
                      spread=1.4, obs_gain=4.0)
-    env = TR.make_env(mode=mode, rows=rows, image_size=image_size, lib=lib)
+    env = make_env(mode=mode, rows=rows, image_size=image_size, lib=lib)
     obs0 = env._obs.cpu().numpy().copy()
     policy = make_policy(spec).bind(env)
     facts = {"lanes": env.sim.rollout_lanes, "launches": env.sim.rollout_launches(N_STEPS),
              "per_launch": env.sim.rollout_steps_per_launch}
-    rec = TR.to_host(env.rollout_policy(policy, N_STEPS, record=TR.record_names() + ("mean", "noise"), call=call))
-    final = TR.snapshot(env)
+    rec = RS.to_host(env.rollout_policy(policy, N_STEPS, record=RS.record_names() + ("mean", "noise"), call=call))
+    final = RS.snapshot(env)
     policy.close()
     env.close()
     _RUNS[key] = dict(rec=rec, final=final, obs0=obs0, spec=spec, facts=facts)
@@ -125,19 +127,19 @@ def test_replay_identity(rows, mode, image_size):
     assert rec["actions"].shape == (N_STEPS, N_ENVS, len(spec["low"])) and np.isfinite(rec["actions"]).all()
     if image_size == 0:  # four staggered lanes, several launches each, some of several steps
         assert run["facts"]["lanes"] == 4 and 1 < run["facts"]["launches"] < N_STEPS
-    env = TR.make_env(mode=mode, rows=rows, image_size=image_size)
-    ep0 = TR.snapshot(env)["episode_i"][:, 12].copy()
-    replay = TR.to_host(env.rollout(torch.as_tensor(rec["actions"], device=env.device), record=TR.record_names()))
-    final = TR.snapshot(env)
+    env = make_env(mode=mode, rows=rows, image_size=image_size)
+    ep0 = RS.snapshot(env)["episode_i"][:, 12].copy()
+    replay = RS.to_host(env.rollout(torch.as_tensor(rec["actions"], device=env.device), record=RS.record_names()))
+    final = RS.snapshot(env)
     env.close()
     assert (final["episode_i"][:, 12] - ep0 >= 2).all()  # every env autoreset twice inside the window
-    for name in TR.record_names():
+    for name in RS.record_names():
         assert rec[name].dtype == replay[name].dtype and rec[name].shape == replay[name].shape, name
         bad = np.argwhere(rec[name] != replay[name])
         assert bad.size == 0, f"record '{name}' differs first at (step, env, ...) = {bad[0].tolist()}"
     if image_size:
         assert final["images"].std() > 0 and final["seg"].max() > 0
-    TR.assert_final(run["final"], final)  # images and seg included, with cameras
+    RS.assert_final(run["final"], final)  # images and seg included, with cameras
     # the clamp was seen to act, and most outputs needed none
     outside = (rec["mean"] < spec["low"]) | (rec["mean"] > spec["high"])
     print("network outputs outside the box:", outside.mean())
@@ -183,8 +185,8 @@ def test_actions_are_the_policy_of_the_observations(rows):
     env = PickPlaceVecEnv(N_ENVS, tasks="all", action_mode="abs_pos", reward_type="staged", randomize_objects=True,
                           max_episode_steps=4, autoreset=False, image_size=0)
     env.sim.step_rows = rows
-    env.reset(seed=TR.SEED)
-    kept = TR.to_host(env.rollout(torch.as_tensor(rec["actions"][:t0 + 1], device=env.device), record=("obs", "done")))
+    env.reset(seed=SEED)
+    kept = RS.to_host(env.rollout(torch.as_tensor(rec["actions"][:t0 + 1], device=env.device), record=("obs", "done")))
     env.close()
     seen = 0
     for t, n in interior:
@@ -203,7 +205,7 @@ _SIM = {}
 
 def eval_sim():
     if "env" not in _SIM:
-        _SIM["env"] = TR.make_env(n=1)
+        _SIM["env"] = make_env(n=1)
     return _SIM["env"]
 
 
@@ -319,9 +321,9 @@ def test_refusals():
     from mujoco_manip_amd.policy import MlpPolicy
     from mujoco_manip_amd.vec_env import PickPlaceVecEnv
 
-    env = TR.make_env(n=2)
+    env = make_env(n=2)
     L, sim = env.sim.L, env.sim.ptr
-    before = TR.snapshot(env)
+    before = RS.snapshot(env)
     W = [np.zeros((8, 85), np.float32), np.zeros((4, 8), np.float32)]
 
     def cfg(n_layers=2, widths=(8, 4), activation=0, weights=W):
@@ -356,15 +358,15 @@ def test_refusals():
     assert L.mmx_rollout_policy(sim, out, 3, 0, C.byref(_lib.MMXPolicyRecord()), None) == -1
     assert L.mmx_rollout_policy(sim, out, -1, 0, C.byref(prec), None) == -1
     assert L.mmx_rollout_policy(sim, out, 0, 0, C.byref(prec), None) == 0
-    rel = TR.make_env(n=2, mode=REL)  # the policy has 4 outputs, this sim's actions 10
+    rel = make_env(n=2, mode=REL)  # the policy has 4 outputs, this sim's actions 10
     assert L.mmx_rollout_policy(rel.sim.ptr, out, 3, 0, C.byref(prec), None) == -1
-    TR.snapshot(rel)
+    RS.snapshot(rel)
     rel.close()
     if torch.cuda.device_count() > 1:  # a policy created on another device
         far = PickPlaceVecEnv(2, action_mode="abs_pos", image_size=0, device=1)
         assert L.mmx_rollout_policy(far.sim.ptr, out, 3, 0, C.byref(prec), None) == -1
         far.close()
-    TR.assert_final(TR.snapshot(env), before)  # nothing was launched
+    RS.assert_final(RS.snapshot(env), before)  # nothing was launched
     assert (acts == -77).all() and (mean == -77).all()
     L.mmx_policy_destroy(out)
     L.mmx_policy_destroy(None)
@@ -379,17 +381,17 @@ def test_refusals():
         env.rollout_policy(policy, -1)
     with pytest.raises(ValueError, match="obs must be"):
         policy.eval(torch.zeros(2, 84))
-    other = TR.make_env(n=2)
+    other = make_env(n=2)
     with pytest.raises(ValueError, match="bound to this env"):
         other.rollout_policy(policy, 3)
     other.close()
     wide = MlpPolicy([(np.zeros((10, 85), np.float32), None)])
     with pytest.raises(ValueError, match="action_dim"):
         wide.bind(env)
-    TR.assert_final(TR.snapshot(env), before)
-    empty = env.rollout_policy(policy, 0, record=TR.record_names() + ("mean", "noise"))
-    assert set(empty) == set(TR.record_names()) | {"actions", "mean", "noise"}
+    RS.assert_final(RS.snapshot(env), before)
+    empty = env.rollout_policy(policy, 0, record=RS.record_names() + ("mean", "noise"))
+    assert set(empty) == set(RS.record_names()) | {"actions", "mean", "noise"}
     assert all(v.shape[:2] == (0, 2) for v in empty.values())
-    TR.assert_final(TR.snapshot(env), before)
+    RS.assert_final(RS.snapshot(env), before)
     policy.close()
     env.close()

@@ -7,15 +7,20 @@ The envs run random per-env, per-step actions with episodes of at most 4 steps a
 every continuation window each env is reset from its own (restored) random stream: spawns and tasks of
 the new episodes only agree if the PCG64 state, its buffered half draw and the sticky episode words came
 back whole."""
+import functools
+
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-REL = "ee_pos_rot6d_g_rel"
+import rollout_support as RS  # noqa: E402
+from rollout_support import REL, assert_same, bits, record_names, to_host, snapshot as host  # noqa: E402
+
 ADIM = {"abs_pos": 4, REL: 10}
 SEED, OTHER_SEED = 7, 1234
+make_env = functools.partial(RS.make_env, seed=SEED)
 
 
 @pytest.fixture(autouse=True)
@@ -24,84 +29,11 @@ def _needs_gpu():
         pytest.skip("needs an MI355X")
 
 
-def _buffers():
-    from mujoco_manip_amd import _lib as L
-
-    return {"qpos": (L.NQ, "<f4"), "qvel": (L.NV, "<f4"), "ctrl": (L.NU, "<f4"), "qacc_warmstart": (L.NV, "<f4"),
-            "obs": (L.NOBS, "<f4"), "reward": (1, "<f4"), "done": (3, "<i4"), "reward_components": (6, "<f4"),
-            "episode_i": (L.EPI_N, "<i4"), "episode_f": (L.EPF_N, "<f4"), "kin": (L.KIN_N, "<f4"), "target": (4, "<f4"),
-            "contacts": (L.MAXCON * L.CON_F, "<f4")}
-
-
 NOT_CAPTURED = ("contacts",)  # diagnostics of the last launch: not in a record (nor are the solver statistics)
 
 
-def host(env) -> dict:
-    """Host copies of every sim-owned buffer (and the camera images, if any), after the queued work."""
-    env.synchronize()
-    torch.cuda.synchronize()
-    out = {k: env.sim.view(k, w, t).cpu().numpy().copy() for k, (w, t) in _buffers().items()}
-    if env._images is not None:
-        out["images"], out["seg"] = env._images.cpu().numpy().copy(), env._seg.cpu().numpy().copy()
-    return out
-
-
-def make_env(n, mode="abs_pos", rows=None, image_size=0, seed=SEED, max_episode_steps=4, render_effects=()):
-    from mujoco_manip_amd.vec_env import PickPlaceVecEnv
-
-    env = PickPlaceVecEnv(n, tasks="all", action_mode=mode, reward_type="staged", randomize_objects=True,
-                          max_episode_steps=max_episode_steps, autoreset=True, image_size=image_size,
-                          render_effects=render_effects)
-    if rows is not None:
-        env.sim.step_rows = rows
-        assert env.sim.step_rows == rows
-    env.reset(seed=seed)
-    return env
-
-
-def make_actions(mode: str, T: int, n: int, seed=99) -> np.ndarray:
-    """Seeded random targets inside the workspace, [T, n, ADIM[mode]]: a different one per env and step."""
-    rng = np.random.default_rng(seed)
-    a = np.zeros((T, n, ADIM[mode]), np.float32)
-    grip = rng.integers(0, 2, (T, n)).astype(np.float32)
-    if mode == "abs_pos":
-        a[..., :3] = rng.uniform([-0.2, 0.3, 0.3], [0.2, 0.5, 0.5], (T, n, 3))
-        a[..., 3] = grip
-    else:  # a small offset from the initial EE pose (T_init of the record), near-identity 6D rotation
-        a[..., :3] = rng.uniform(-0.1, 0.1, (T, n, 3))
-        a[..., 3:9] = np.array([1, 0, 0, 0, 1, 0], np.float32) + rng.uniform(-0.05, 0.05, (T, n, 6))
-        a[..., 9] = grip
-    return a
-
-
-def record_names():
-    from mujoco_manip_amd import _lib
-
-    return tuple(_lib.TRAJ_FIELDS)
-
-
-def to_host(rec: dict) -> dict:
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in rec.items()}
-
-
-def bits(a: np.ndarray) -> np.ndarray:
-    """The array's bytes as unsigned integers of its item size (a NaN equals itself, -0.0 differs from 0.0)."""
-    return np.ascontiguousarray(a).view({1: np.uint8, 4: np.uint32}[a.dtype.itemsize])
-
-
-def assert_same(got: dict, want: dict, skip=(), envs=None, axis=0, what=""):
-    """Every array of `want` equals `got`'s, bit for bit; envs: only these indices along `axis`."""
-    assert set(got) == set(want)
-    for name in want:
-        if name in skip:
-            continue
-        g, w = got[name], want[name]
-        assert g.shape == w.shape and g.dtype == w.dtype, name
-        if envs is not None:
-            g, w = np.take(g, envs, axis=axis), np.take(w, envs, axis=axis)
-        bad = np.argwhere(bits(g) != bits(w))
-        assert bad.size == 0, f"{what} '{name}' differs first at {bad[0].tolist()} ({len(bad)} words)"
+def make_actions(mode, T, n, seed=99):
+    return RS.make_actions(mode, T, n, seed=seed, widths=ADIM)
 
 
 def full_rollout(env, acts):

@@ -9,7 +9,7 @@ The given-action case runs 10 envs on four rollout lanes (MMX_STREAMS=4: uneven 
 launch plan with launches of one, two and three steps) for 11 steps with episodes of at most 4 steps, so
 every env autoresets twice inside the window, mostly in the middle of a launch; the actions differ per
 env and per step, so a wrong step index or env index shows."""
-import hashlib
+import functools
 
 import numpy as np
 import pytest
@@ -17,56 +17,14 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
+import rollout_support as RS  # noqa: E402
+from rollout_support import REL, assert_final, assert_record, digest, record_names, snapshot, to_host  # noqa: E402
+
 N_ENVS, N_STEPS, SEED = 10, 11, 7
-REL = "ee_pos_rot6d_g_rel"
 # (action mode, action_dim passed to the library): the relative 6D mode needs 10, passed wider
 MODES = {"abs_pos": 4, REL: 12}
-
-
-def _buffers():
-    from mujoco_manip_amd import _lib as L
-
-    return {"qpos": (L.NQ, "<f4"), "qvel": (L.NV, "<f4"), "ctrl": (L.NU, "<f4"), "qacc_warmstart": (L.NV, "<f4"),
-            "obs": (L.NOBS, "<f4"), "reward": (1, "<f4"), "done": (3, "<i4"), "reward_components": (6, "<f4"),
-            "episode_i": (L.EPI_N, "<i4"), "episode_f": (L.EPF_N, "<f4"), "kin": (L.KIN_N, "<f4"), "target": (4, "<f4"),
-            "contacts": (L.MAXCON * L.CON_F, "<f4")}
-
-
-def snapshot(env) -> dict:
-    """Host copies of every sim-owned buffer (and the camera images, if any), after the queued work."""
-    env.synchronize()
-    torch.cuda.synchronize()
-    out = {k: env.sim.view(k, w, t).cpu().numpy().copy() for k, (w, t) in _buffers().items()}
-    if env._images is not None:
-        out["images"], out["seg"] = env._images.cpu().numpy().copy(), env._seg.cpu().numpy().copy()
-    return out
-
-
-def make_env(n=N_ENVS, mode="abs_pos", rows=128, image_size=0, seed=SEED, max_episode_steps=4, lib=None):
-    from mujoco_manip_amd.vec_env import PickPlaceVecEnv
-
-    env = PickPlaceVecEnv(n, tasks="all", action_mode=mode, reward_type="staged", randomize_objects=True,
-                          max_episode_steps=max_episode_steps, autoreset=True, image_size=image_size, lib=lib)
-    env.sim.step_rows = rows
-    assert env.sim.step_rows == rows
-    env.reset(seed=seed)
-    return env
-
-
-def make_actions(mode: str, T: int, n: int) -> np.ndarray:
-    """Seeded random targets inside the workspace, [T, n, MODES[mode]]: a different one per env and step."""
-    rng = np.random.default_rng(1234)
-    a = np.zeros((T, n, MODES[mode]), np.float32)
-    grip = rng.integers(0, 2, (T, n)).astype(np.float32)
-    if mode == "abs_pos":
-        a[..., :3] = rng.uniform([-0.2, 0.3, 0.3], [0.2, 0.5, 0.5], (T, n, 3))
-        a[..., 3] = grip
-    else:  # a small offset from the initial EE pose, near-identity 6D rotation; columns 10, 11 are not read
-        a[..., :3] = rng.uniform(-0.1, 0.1, (T, n, 3))
-        a[..., 3:9] = np.array([1, 0, 0, 0, 1, 0], np.float32) + rng.uniform(-0.05, 0.05, (T, n, 6))
-        a[..., 9] = grip
-        a[..., 10:] = rng.uniform(-1e3, 1e3, (T, n, 2))
-    return a
+make_env = functools.partial(RS.make_env, n=N_ENVS, rows=128, seed=SEED)
+make_actions = functools.partial(RS.make_actions, seed=1234, widths=MODES)
 
 
 def stepwise(env, acts) -> list:
@@ -76,42 +34,6 @@ def stepwise(env, acts) -> list:
         env.sim.step(acts[k].data_ptr(), acts.shape[2])
         snaps.append(snapshot(env))
     return snaps
-
-
-def record_names():
-    from mujoco_manip_amd import _lib
-
-    return tuple(_lib.TRAJ_FIELDS)
-
-
-def to_host(rec: dict) -> dict:
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in rec.items()}
-
-
-def assert_record(rec: dict, snaps: list, skip=()):
-    assert set(rec) == set(record_names())
-    for name in record_names():
-        if name in skip:
-            continue
-        want = np.stack([s[name] for s in snaps])
-        assert rec[name].shape == want.shape and rec[name].dtype == want.dtype, name
-        bad = np.argwhere(rec[name] != want)
-        assert bad.size == 0, f"record '{name}' differs first at (step, env, ...) = {bad[0].tolist()}"
-
-
-def assert_final(got: dict, want: dict):
-    assert set(got) == set(want)
-    for name in want:
-        bad = np.argwhere(got[name] != want[name])
-        assert bad.size == 0, f"buffer '{name}' differs first at {bad[0].tolist()}"
-
-
-def digest(rec: dict) -> str:
-    h = hashlib.sha256()
-    for name in record_names():
-        h.update(np.ascontiguousarray(rec[name]).tobytes())
-    return h.hexdigest()
 
 
 # ------------------------------------------------------------------ 1. given actions
