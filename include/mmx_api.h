@@ -416,6 +416,51 @@ int  mmx_policy_fit(mmx_policy* p, const float* obs_dev, const float* target_dev
 int  mmx_policy_get_weights(mmx_policy* p, float* const* weight_host, float* const* bias_host);
 int  mmx_policy_set_weights(mmx_policy* p, const float* const* weight_host, const float* const* bias_host);
 
+/* Policy-gradient fits on the device (no reference counterpart): generalised advantage estimation (Schulman et al.
+ * 2016) over a rollout record, and PPO's clipped surrogate (Schulman et al. 2017) as a second objective of the fit
+ * above.  A critic is an mmx_policy of width 1 (log_std, low, high NULL) fitted with mmx_policy_fit on the returns;
+ * roll out -> mmx_policy_eval of the critic -> mmx_gae -> mmx_policy_fit_pg and mmx_policy_fit -> roll out runs
+ * with the observations, actions and weights never leaving the device.  Everything is fp32 in a stated operation
+ * order (csrc/mmx_pg.h), without atomics: the same call on the same state gives the same bits every time.
+ * mmx_gae: per env column i, t from T - 1 down to 0,
+ *     end   = done[t][i][0] != 0 (terminated) || done[t][i][1] != 0 (truncated)
+ *     nv    = end ? 0 : (t == T - 1 ? value_last[i] : value[t + 1][i])
+ *     delta = fma(gamma, nv, reward[t][i]) - value[t][i]
+ *     adv[t][i] = end ? delta : fma(gamma lambda, adv[t + 1][i], delta);      ret[t][i] = adv[t][i] + value[t][i]
+ * value[t][i] = V of the observation env i held before step t, value_last[i] = V of the observation after the last
+ * step.  A truncated step takes next value 0 like a terminated one: the record keeps the new episode's first
+ * observation, not the ended one's last, so the cut-off state's value cannot be evaluated from it.  normalize != 0
+ * rescales adv_out (not ret_out) afterwards over all n = T N entries: mean = sum / n, var = sum (x - mean)^2 / n,
+ * adv = (adv - mean) / (sqrt(var) + 1e-8), both sums in an order fixed by n alone.  Device pointers; asynchronous on
+ * the sim's stream; N need not be the sim's num_envs; ret_out_dev may be NULL.  T == 0 returns MMX_OK; MMX_EINVAL,
+ * with nothing launched, for a NULL sim, cfg or required pointer, T < 0, N < 1, T N > 2^31 - 1, gamma or lambda
+ * outside [0, 1] or not finite.
+ * mmx_policy_fit_pg: mmx_policy_fit with the objective (B = cfg->fit.batch, pairs p_s drawn as there)
+ *     L = -1 / B sum_{s < B} min(r_s Adv[p_s], clamp(r_s, 1 - clip, 1 + clip) Adv[p_s]),
+ *     r_s = exp(sum_a 0.5 (z_a^2 - z'_a^2)),  z = noise[p_s],  z'_a = (fma(std_a, z_a, mean_old[p_s][a]) - mean_a) / std_a
+ * the ratio of the Gaussian densities, now and at the rollout, of the sample BEFORE the clamp (the clamp is part of
+ * the environment); mean = the network's output now; mean_old_dev and noise_dev [n_pairs][A] are a rollout's
+ * mmx_policy_record, adv_dev [n_pairs] mmx_gae's output.  std = exp(log_std) is not trained: with it fixed the ratio
+ * needs nothing else.  stats_out_dev [n_steps][3] (device) or NULL: per step, before its update, the surrogate loss
+ * L, the approximate KL 1 / B sum ((r_s - 1) - log r_s), and the fraction of samples whose gradient the clip removed.
+ * m, v, t, the batch draw, the workspace, stream ordering and the in-place update are mmx_policy_fit's, shared with
+ * it: a step of either objective advances the same t.
+ * MMX_EINVAL, with nothing touched, for everything mmx_policy_fit refuses (mean_old_dev, noise_dev and adv_dev are
+ * required), a deterministic policy (created without log_std, or any std[a] == 0 for a < A), clip not finite or
+ * outside (0, 1).
+ * mmx_policy_set_log_std: std[a] = exp(log_std_host[a]) evaluated on the host in fp64 as mmx_policy_create does, written
+ * into the policy in place on the stream (returns when the copy is done); nothing else of the policy changes, and a
+ * policy created without log_std draws noise from then on.  MMX_EINVAL for a NULL argument or an entry not finite. */
+typedef struct { float gamma, lambda; int32_t normalize; } mmx_gae_config;
+int  mmx_gae(mmx_sim* sim, const mmx_gae_config* cfg, int32_t T, int32_t N, const float* reward_dev,
+             const int32_t* done_dev, const float* value_dev, const float* value_last_dev, float* adv_out_dev,
+             float* ret_out_dev);
+typedef struct { mmx_fit_config fit; float clip; } mmx_pg_config;
+int  mmx_policy_fit_pg(mmx_policy* p, const float* obs_dev, const float* mean_old_dev, const float* noise_dev,
+                       const float* adv_dev, int64_t n_pairs, int32_t n_steps, const mmx_pg_config* cfg,
+                       float* stats_out_dev);
+int  mmx_policy_set_log_std(mmx_policy* p, const float* log_std_host);
+
 /* DAgger rollouts (Ross et al. 2011; no reference counterpart): mmx_rollout_policy with the FSM expert beside the
  * learner, in the same fused launches (lanes, launch plan, dispatch order, both camera paths; with cameras the
  * numeric observation is read and the images hold the last frame).  Per rollout step t and env i, inside the launch:

@@ -7,7 +7,7 @@ environments in lockstep by HIP kernels (libmmx.so, C-ABI in include/mmx_api.h).
 """
 from .constants import ACTION_REPEAT, ALL_TASKS, BINS, OBJECTS, TASK_SETS  # noqa: F401
 
-__all__ = ["PickPlaceVecEnv", "PickPlaceGymEnv", "Snapshot", "MppiPlanner", "MlpPolicy", "DaggerBuffer", "build_library",
+__all__ = ["PickPlaceVecEnv", "PickPlaceGymEnv", "Snapshot", "MppiPlanner", "MlpPolicy", "MlpCritic", "DaggerBuffer", "build_library",
            "episode_seed"]
 
 
@@ -40,6 +40,10 @@ def __getattr__(name):
         from .policy import MlpPolicy
 
         return MlpPolicy
+    if name == "MlpCritic":
+        from .policy import MlpCritic
+
+        return MlpCritic
     if name == "DaggerBuffer":
         from .dagger import DaggerBuffer
 

@@ -144,6 +144,16 @@ class MMXFitConfig(C.Structure):
                 ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("seed", C.c_uint64)]
 
 
+class MMXGaeConfig(C.Structure):
+    """mmx_gae_config (include/mmx_api.h): discount, lambda and whether mmx_gae normalises the advantages."""
+    _fields_ = [("gamma", C.c_float), ("lambda_", C.c_float), ("normalize", C.c_int32)]
+
+
+class MMXPgConfig(C.Structure):
+    """mmx_pg_config (include/mmx_api.h): mmx_policy_fit's configuration and the surrogate's clip range."""
+    _fields_ = [("fit", MMXFitConfig), ("clip", C.c_float)]
+
+
 class MMXDaggerConfig(C.Structure):
     """mmx_dagger_config (include/mmx_api.h): the gate of mmx_rollout_dagger."""
     _fields_ = [("beta", C.c_float), ("takeover_dist", C.c_float)]
@@ -226,6 +236,9 @@ _PROTOS = {
     "mmx_policy_fit": (C.c_int, [_vp, _vp, _vp, _i64, _i32, C.POINTER(MMXFitConfig), _vp]),
     "mmx_policy_get_weights": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "mmx_policy_set_weights": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "mmx_gae": (C.c_int, [_vp, C.POINTER(MMXGaeConfig), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mmx_policy_fit_pg": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, C.POINTER(MMXPgConfig), _vp]),
+    "mmx_policy_set_log_std": (C.c_int, [_vp, _fp]),
     "mmx_rollout_dagger": (C.c_int, [_vp, _vp, _i32, C.c_uint64, C.POINTER(MMXDaggerConfig), C.POINTER(MMXDaggerRecord),
                                      C.POINTER(MMXTrajectory)]),
     "mmx_png_bound": (_i64, [_i32, _i32]),
@@ -687,6 +700,14 @@ class Sim(_Owner):
         sim's stream): the forward solve and mj_contactForce into the arrays of force_views()."""
         self._check(self.L.mmx_contact_forces(self.ptr), "mmx_contact_forces")
 
+    def gae(self, cfg: "MMXGaeConfig", T: int, N: int, reward_ptr: int, done_ptr: int, value_ptr: int, value_last_ptr: int,
+            adv_ptr: int, ret_ptr: int | None = None):
+        """GAE(lambda) over a [T][N] record into adv (and ret) at the device pointers (mmx_gae; asynchronous on the
+        sim's stream)."""
+        self._check(self.L.mmx_gae(self.ptr, C.byref(cfg), int(T), int(N), C.c_void_p(reward_ptr), C.c_void_p(done_ptr),
+                                   C.c_void_p(value_ptr), C.c_void_p(value_last_ptr), C.c_void_p(adv_ptr),
+                                   C.c_void_p(ret_ptr) if ret_ptr else None), "mmx_gae")
+
     def force_views(self) -> dict:
         """Zero-copy torch views of the contact-force pass's outputs (mmx_force_buffers), valid until the sim
         closes; they exist from the first contact_forces() call on."""
@@ -832,6 +853,20 @@ class Policy(_Owner):
         stream)."""
         self.sim._check(self.L.mmx_policy_fit(self.ptr, C.c_void_p(obs_ptr), C.c_void_p(target_ptr), int(n_pairs), int(n_steps),
                                               C.byref(cfg), C.c_void_p(loss_ptr) if loss_ptr else None), "mmx_policy_fit")
+
+    def fit_pg(self, obs_ptr: int, mean_old_ptr: int, noise_ptr: int, adv_ptr: int, n_pairs: int, n_steps: int, cfg: MMXPgConfig,
+               stats_ptr: int | None = None):
+        """n_steps steps of PPO's clipped surrogate on the samples (obs [n][85], mean_old and noise [n][A], adv [n]:
+        device pointers) that update the weights in place; stats_ptr: device [n_steps][3] or None (mmx_policy_fit_pg,
+        asynchronous on the creating sim's stream)."""
+        self.sim._check(self.L.mmx_policy_fit_pg(self.ptr, C.c_void_p(obs_ptr), C.c_void_p(mean_old_ptr), C.c_void_p(noise_ptr),
+                                                 C.c_void_p(adv_ptr), int(n_pairs), int(n_steps), C.byref(cfg),
+                                                 C.c_void_p(stats_ptr) if stats_ptr else None), "mmx_policy_fit_pg")
+
+    def set_log_std(self, log_std):
+        """std = exp(log_std [A]) into the device blob, in place (mmx_policy_set_log_std)."""
+        a = np.ascontiguousarray(log_std, np.float32)
+        self.sim._check(self.L.mmx_policy_set_log_std(self.ptr, a.ctypes.data_as(_fp)), "mmx_policy_set_log_std")
 
     def get_weights(self) -> list:
         """[(W [out, in], b [out]), ...] float32 numpy arrays of the weights as they are now (mmx_policy_get_weights;

@@ -19,6 +19,7 @@
 #include "mmx_dagger.h"
 #include "mmx_launch.h"
 #include "mmx_mppi.h"
+#include "mmx_pg.h"
 #include "mmx_plan.h"
 #include "mmx_policy.h"
 #include "mmx_policy_fit.h"
@@ -95,6 +96,8 @@ struct mmx_sim {
   int* q_task = nullptr;
   unsigned long long* q_rng = nullptr;
   int q_n = -1;
+  // mmx_gae's normalisation: the mean and the denominator (two floats, allocated at the first normalised call)
+  float* pg_moments = nullptr;
 };
 
 // A planner bound to its (camera-less) planner sim: the launch parameters, its device arrays (its own
@@ -124,6 +127,9 @@ struct mmx_policy {
   float* fit_ws = nullptr;
   int fit_batch = 0;
   uint64_t fit_t = 0;
+  // the blob's std entries as the host last wrote them (mmx_policy_create, mmx_policy_set_log_std): what
+  // mmx_policy_fit_pg asks for a stochastic policy without reading the device
+  float std_host[MMX_MPPI_MAX_ADIM] = {};
 };
 
 namespace {
@@ -1076,6 +1082,7 @@ int mmx_policy_create(mmx_sim* sim, const mmx_policy_config* c, mmx_policy** out
   P.seed_lo = (uint32_t)c->seed, P.seed_hi = (uint32_t)(c->seed >> 32);
   std::vector<float> blob(policy_layout(P));
   policy_pack(P, c->weight, c->bias, c->obs_shift, c->obs_scale, c->log_std, c->low, c->high, blob.data());
+  std::copy(blob.begin() + P.std_off, blob.begin() + P.std_off + MMX_MPPI_MAX_ADIM, p->std_host);
   DeviceGuard guard(sim);
   void* d = nullptr;
   if (hipMalloc(&d, blob.size() * sizeof(float)) != hipSuccess) {
@@ -1109,66 +1116,153 @@ int mmx_policy_eval(mmx_policy* p, const float* obs_dev, int32_t n, float* mean_
   return hip_check(p->sim, mmx_launch_policy_eval(&p->P, obs_dev, n, mean_out_dev, p->sim->stream), "mmx_policy_eval");
 }
 
-// The policy's training step (mmx_policy_fit.h; mmx_policy_fit.hip): n_steps times three launches on the stream
-int mmx_policy_fit(mmx_policy* p, const float* obs_dev, const float* target_dev, int64_t n_pairs, int32_t n_steps,
-                   const mmx_fit_config* c, float* loss_out_dev) {
-  if (!p) return MMX_EINVAL;
-  mmx_sim* sim = p->sim;
-  if (!obs_dev || !target_dev || !c) return fail(sim, MMX_EINVAL, "mmx_policy_fit: NULL argument");
-  if (n_pairs < 1 || n_pairs > INT32_MAX || n_steps < 0) return fail(sim, MMX_EINVAL, "mmx_policy_fit: n_pairs outside 1 .. 2^31 - 1 or n_steps < 0");
-  if (c->batch < 1 || c->batch > MMX_FIT_MAX_BATCH) return fail(sim, MMX_EINVAL, "mmx_policy_fit: batch outside 1 .. 65536");
-  if (c->optimizer != MMX_FIT_SGD && c->optimizer != MMX_FIT_ADAM) return fail(sim, MMX_EINVAL, "mmx_policy_fit: unknown optimizer");
+// What mmx_policy_fit and mmx_policy_fit_pg ask of their common arguments (`data_ok`: the caller's own pointers),
+// each refusal under the caller's name
+static int policy_fit_args(mmx_sim* sim, const char* who, bool data_ok, int64_t n_pairs, int32_t n_steps, const mmx_fit_config* c) {
+  const std::string w(who);
+  if (!data_ok || !c) return fail(sim, MMX_EINVAL, w + ": NULL argument");
+  if (n_pairs < 1 || n_pairs > INT32_MAX || n_steps < 0) return fail(sim, MMX_EINVAL, w + ": n_pairs outside 1 .. 2^31 - 1 or n_steps < 0");
+  if (c->batch < 1 || c->batch > MMX_FIT_MAX_BATCH) return fail(sim, MMX_EINVAL, w + ": batch outside 1 .. 65536");
+  if (c->optimizer != MMX_FIT_SGD && c->optimizer != MMX_FIT_ADAM) return fail(sim, MMX_EINVAL, w + ": unknown optimizer");
   // (written so that a NaN fails every test)
   if (!(c->lr > 0.f && c->lr <= FLT_MAX) || !(c->eps > 0.f && c->eps <= FLT_MAX))
-    return fail(sim, MMX_EINVAL, "mmx_policy_fit: lr or eps not finite or <= 0");
+    return fail(sim, MMX_EINVAL, w + ": lr or eps not finite or <= 0");
   if (!(c->beta1 >= 0.f && c->beta1 < 1.f) || !(c->beta2 >= 0.f && c->beta2 < 1.f))
-    return fail(sim, MMX_EINVAL, "mmx_policy_fit: a beta outside [0, 1)");
-  if (n_steps == 0) return MMX_OK;
-  DeviceGuard guard(sim);
+    return fail(sim, MMX_EINVAL, w + ": a beta outside [0, 1)");
+  return MMX_OK;
+}
+// The state both fits share, made ready for a call of n_steps > 0: m and v (allocated and cleared at the first fit),
+// the workspace of a batch of c->batch (grown behind a stream synchronisation; it always holds the PG statistics'
+// partials too), the optimiser's reset; then F's and G's fields that do not depend on the objective
+static int policy_fit_prepare(mmx_policy* p, const char* who, const mmx_fit_config* c, const float* obs_dev, int64_t n_pairs, MmxFit* F,
+                              MmxPg* G) {
+  mmx_sim* sim = p->sim;
+  const std::string w(who);
   const MmxPolicy& P = p->P;
   const size_t params = policy_fit_param_floats(P);
   if (!p->fit_m) {
     void *m = nullptr, *v = nullptr;
     if (hipMalloc(&m, params * sizeof(float)) != hipSuccess || hipMalloc(&v, params * sizeof(float)) != hipSuccess) {
       if (m) (void)hipFree(m);
-      return fail(sim, MMX_ENOMEM, "mmx_policy_fit: device allocation");
+      return fail(sim, MMX_ENOMEM, w + ": device allocation");
     }
     p->fit_m = static_cast<float*>(m), p->fit_v = static_cast<float*>(v);
     if (hipMemsetAsync(m, 0, params * sizeof(float), sim->stream) != hipSuccess ||
         hipMemsetAsync(v, 0, params * sizeof(float), sim->stream) != hipSuccess)
-      return fail(sim, MMX_EDEVICE, "mmx_policy_fit: clearing the optimiser state");
+      return fail(sim, MMX_EDEVICE, w + ": clearing the optimiser state");
   }
   if (c->batch > p->fit_batch) {
     if (p->fit_ws) {  // launches queued by an earlier call may still use it
-      if (hipStreamSynchronize(sim->stream) != hipSuccess) return fail(sim, MMX_EDEVICE, "mmx_policy_fit sync");
+      if (hipStreamSynchronize(sim->stream) != hipSuccess) return fail(sim, MMX_EDEVICE, w + " sync");
       (void)hipFree(p->fit_ws);
       p->fit_ws = nullptr, p->fit_batch = 0;
     }
-    void* w = nullptr;
-    if (hipMalloc(&w, mmx_policy_fit_workspace_floats(&P, c->batch, nullptr) * sizeof(float)) != hipSuccess)
-      return fail(sim, MMX_ENOMEM, "mmx_policy_fit: device allocation (workspace)");
-    p->fit_ws = static_cast<float*>(w), p->fit_batch = c->batch;
+    void* ws = nullptr;
+    if (hipMalloc(&ws, mmx_policy_fit_pg_workspace_floats(&P, c->batch, nullptr, nullptr) * sizeof(float)) != hipSuccess)
+      return fail(sim, MMX_ENOMEM, w + ": device allocation (workspace)");
+    p->fit_ws = static_cast<float*>(ws), p->fit_batch = c->batch;
   }
   if (c->reset_optimizer) {
     if (hipMemsetAsync(p->fit_m, 0, params * sizeof(float), sim->stream) != hipSuccess ||
         hipMemsetAsync(p->fit_v, 0, params * sizeof(float), sim->stream) != hipSuccess)
-      return fail(sim, MMX_EDEVICE, "mmx_policy_fit: clearing the optimiser state");
+      return fail(sim, MMX_EDEVICE, w + ": clearing the optimiser state");
     p->fit_t = 0;
   }
+  F->obs = obs_dev, F->n = n_pairs, F->ws = p->fit_ws;
+  (void)mmx_policy_fit_pg_workspace_floats(&P, c->batch, F, G);
+  F->seed_lo = (uint32_t)c->seed, F->seed_hi = (uint32_t)(c->seed >> 32);
+  F->B = c->batch, F->shuffle = c->shuffle != 0;
+  F->inv_count = policy_fit_inv_count(c->batch, P.A), F->dscale = 2.f * F->inv_count;
+  return MMX_OK;
+}
+
+// The policy's training step (mmx_policy_fit.h; mmx_policy_fit.hip): n_steps times three launches on the stream
+int mmx_policy_fit(mmx_policy* p, const float* obs_dev, const float* target_dev, int64_t n_pairs, int32_t n_steps,
+                   const mmx_fit_config* c, float* loss_out_dev) {
+  if (!p) return MMX_EINVAL;
+  mmx_sim* sim = p->sim;
+  if (const int rc = policy_fit_args(sim, "mmx_policy_fit", obs_dev && target_dev, n_pairs, n_steps, c)) return rc;
+  if (n_steps == 0) return MMX_OK;
+  DeviceGuard guard(sim);
   MmxFit F{};
-  F.obs = obs_dev, F.target = target_dev, F.n = n_pairs, F.ws = p->fit_ws;
-  (void)mmx_policy_fit_workspace_floats(&P, c->batch, &F);
-  F.seed_lo = (uint32_t)c->seed, F.seed_hi = (uint32_t)(c->seed >> 32);
-  F.B = c->batch, F.shuffle = c->shuffle != 0;
-  F.inv_count = policy_fit_inv_count(c->batch, P.A), F.dscale = 2.f * F.inv_count;
+  MmxPg G{};
+  if (const int rc = policy_fit_prepare(p, "mmx_policy_fit", c, obs_dev, n_pairs, &F, &G)) return rc;
+  F.target = target_dev;
   for (int32_t i = 0; i < n_steps; i++) {
     F.k = p->fit_t++;
     const MmxFitOpt O = policy_fit_opt(c->optimizer, c->lr, c->beta1, c->beta2, c->eps, p->fit_t);
-    const hipError_t e = mmx_launch_policy_fit_step(&P, &F, &O, p->data, p->fit_m, p->fit_v,
+    const hipError_t e = mmx_launch_policy_fit_step(&p->P, &F, &O, p->data, p->fit_m, p->fit_v,
                                                     loss_out_dev ? loss_out_dev + i : nullptr, sim->stream);
     if (e != hipSuccess) return hip_check(sim, e, "mmx_policy_fit");
   }
   return MMX_OK;
+}
+
+// The policy-gradient step (mmx_pg.h; mmx_policy_fit.hip): the same state and workspace, PPO's clipped surrogate as
+// the output delta, n_steps times four launches on the stream.  std_host: the policy's std as the blob holds it
+int mmx_policy_fit_pg(mmx_policy* p, const float* obs_dev, const float* mean_old_dev, const float* noise_dev, const float* adv_dev,
+                      int64_t n_pairs, int32_t n_steps, const mmx_pg_config* c, float* stats_out_dev) {
+  if (!p) return MMX_EINVAL;
+  mmx_sim* sim = p->sim;
+  if (const int rc = policy_fit_args(sim, "mmx_policy_fit_pg", obs_dev && mean_old_dev && noise_dev && adv_dev, n_pairs, n_steps,
+                                     c ? &c->fit : nullptr))
+    return rc;
+  if (!(c->clip > 0.f && c->clip < 1.f)) return fail(sim, MMX_EINVAL, "mmx_policy_fit_pg: clip not finite or outside (0, 1)");
+  for (int a = 0; a < p->P.A; a++)
+    if (!(p->std_host[a] > 0.f))
+      return fail(sim, MMX_EINVAL, "mmx_policy_fit_pg: a deterministic policy (no log_std, or a std of 0) has no likelihood ratio");
+  if (n_steps == 0) return MMX_OK;
+  DeviceGuard guard(sim);
+  MmxFit F{};
+  MmxPg G{};
+  if (const int rc = policy_fit_prepare(p, "mmx_policy_fit_pg", &c->fit, obs_dev, n_pairs, &F, &G)) return rc;
+  G.mean_old = mean_old_dev, G.noise = noise_dev, G.adv = adv_dev;
+  G.invB = pg_inv_batch(c->fit.batch), G.lo = 1.f - c->clip, G.hi = 1.f + c->clip;
+  for (int32_t i = 0; i < n_steps; i++) {
+    F.k = p->fit_t++;
+    const MmxFitOpt O = policy_fit_opt(c->fit.optimizer, c->fit.lr, c->fit.beta1, c->fit.beta2, c->fit.eps, p->fit_t);
+    const hipError_t e = mmx_launch_policy_fit_pg_step(&p->P, &F, &G, &O, p->data, p->fit_m, p->fit_v,
+                                                       stats_out_dev ? stats_out_dev + 3 * (size_t)i : nullptr, sim->stream);
+    if (e != hipSuccess) return hip_check(sim, e, "mmx_policy_fit_pg");
+  }
+  return MMX_OK;
+}
+
+// exp(log_std) as mmx_policy_create evaluates it, into the blob's std entries in place on the stream
+int mmx_policy_set_log_std(mmx_policy* p, const float* log_std_host) {
+  if (!p) return MMX_EINVAL;
+  if (!log_std_host) return fail(p->sim, MMX_EINVAL, "mmx_policy_set_log_std: NULL argument");
+  float sd[MMX_MPPI_MAX_ADIM] = {};
+  for (int a = 0; a < p->P.A; a++) {
+    if (!(log_std_host[a] >= -FLT_MAX && log_std_host[a] <= FLT_MAX)) return fail(p->sim, MMX_EINVAL, "mmx_policy_set_log_std: an entry that is not finite");
+    sd[a] = (float)exp((double)log_std_host[a]);
+  }
+  DeviceGuard guard(p->sim);
+  // (synchronised: the host array is this frame's)
+  if (hipMemcpyAsync(p->data + p->P.std_off, sd, sizeof(sd), hipMemcpyHostToDevice, p->sim->stream) != hipSuccess ||
+      hipStreamSynchronize(p->sim->stream) != hipSuccess)
+    return fail(p->sim, MMX_EDEVICE, "mmx_policy_set_log_std: upload");
+  std::copy(sd, sd + MMX_MPPI_MAX_ADIM, p->std_host);
+  p->P.stochastic = 1;
+  return MMX_OK;
+}
+
+// Generalised advantage estimation over a rollout record (mmx_pg.h), and the advantages' normalisation
+int mmx_gae(mmx_sim* sim, const mmx_gae_config* c, int32_t T, int32_t N, const float* reward_dev, const int32_t* done_dev,
+            const float* value_dev, const float* value_last_dev, float* adv_out_dev, float* ret_out_dev) {
+  if (!sim) return MMX_EINVAL;
+  if (!c || !reward_dev || !done_dev || !value_dev || !value_last_dev || !adv_out_dev) return fail(sim, MMX_EINVAL, "mmx_gae: NULL argument");
+  if (T < 0 || N < 1 || (int64_t)T * (int64_t)N > INT32_MAX) return fail(sim, MMX_EINVAL, "mmx_gae: T < 0, N < 1 or T N > 2^31 - 1");
+  if (!(c->gamma >= 0.f && c->gamma <= 1.f) || !(c->lambda >= 0.f && c->lambda <= 1.f))
+    return fail(sim, MMX_EINVAL, "mmx_gae: gamma or lambda outside [0, 1] or not finite");
+  if (T == 0) return MMX_OK;
+  DeviceGuard guard(sim);
+  if (c->normalize && !sim->pg_moments) {
+    sim->pg_moments = dalloc<float>(sim, 2);
+    if (!sim->pg_moments) return fail(sim, MMX_ENOMEM, "mmx_gae: device allocation");
+  }
+  return hip_check(sim, mmx_launch_gae(c->gamma, c->gamma * c->lambda, T, N, reward_dev, done_dev, value_dev, value_last_dev, adv_out_dev,
+                                       ret_out_dev, c->normalize ? sim->pg_moments : nullptr, sim->stream), "mmx_gae");
 }
 
 int mmx_policy_get_weights(mmx_policy* p, float* const* weight_host, float* const* bias_host) {

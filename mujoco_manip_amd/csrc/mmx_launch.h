@@ -16,6 +16,7 @@ struct MMXPolicyRec;
 struct MMXDagger;
 struct MmxFit;
 struct MmxFitOpt;
+struct MmxPg;
 
 extern "C" {
 
@@ -98,6 +99,14 @@ hipError_t mmx_launch_policy_eval(const MmxPolicy* P, const float* obs, int n, f
 size_t mmx_policy_fit_workspace_floats(const MmxPolicy* P, int B, MmxFit* F);
 hipError_t mmx_launch_policy_fit_step(const MmxPolicy* P, const MmxFit* F, const MmxFitOpt* O, float* blob, float* m, float* v,
                                       float* loss_out, hipStream_t st);
+// the policy-gradient step (MmxPg: mmx_pg.h): the workspace with the statistics' partials behind it (G, when not
+// null, gets stat_base), and one step's launches; stats_out: three floats or null.  mmx_launch_gae: the advantages
+// of a [T][N] record, normalised in place when `moments` (two device floats of scratch) is not null
+size_t mmx_policy_fit_pg_workspace_floats(const MmxPolicy* P, int B, MmxFit* F, MmxPg* G);
+hipError_t mmx_launch_policy_fit_pg_step(const MmxPolicy* P, const MmxFit* F, const MmxPg* G, const MmxFitOpt* O, float* blob, float* m,
+                                         float* v, float* stats_out, hipStream_t st);
+hipError_t mmx_launch_gae(float gamma, float gl, int T, int N, const float* reward, const int32_t* done, const float* value,
+                          const float* value_last, float* adv_out, float* ret_out, float* moments, hipStream_t st);
 
 }  // extern "C"
 

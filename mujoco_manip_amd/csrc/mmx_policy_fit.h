@@ -125,17 +125,17 @@ inline size_t policy_fit_param_floats(const MmxPolicy& P) { return (size_t)P.shi
 // forward pass of policy_forward_ref with every layer's activations kept, the deltas, the gradients summed over the
 // batch in index order (one fused multiply-add chain from 0 per weight), and the update of every real weight and
 // bias.  The padding columns are neither read into a sum nor written: they stay exactly 0.  m, v:
-// policy_fit_param_floats(P) floats, indexed like the blob (untouched by SGD).  Returns the batch loss before the
-// update: the squared errors summed in (s, a) order, one fused chain, times 1 / (B A).
-inline float policy_fit_step_ref(const MmxPolicy& P, float* blob, const float* obs, const float* target, int64_t n, int B,
-                                 int shuffle, uint64_t seed, uint64_t k, const MmxFitOpt& opt, float* m, float* v) {
+// policy_fit_param_floats(P) floats, indexed like the blob (untouched by SGD).
+// The objective is the caller's: out_delta(s, p, mean, d) gets sample s (pair p) with the network's output mean [A],
+// writes the output delta d [A] and keeps whatever it sums (the loss, the statistics), samples in order.
+template <class OutDelta>
+inline void policy_step_ref(const MmxPolicy& P, float* blob, const float* obs, int64_t n, int B, int shuffle, uint64_t seed,
+                            uint64_t k, const MmxFitOpt& opt, float* m, float* v, OutDelta&& out_delta) {
   const int L = P.n_layers, A = P.A;
-  const float inv = policy_fit_inv_count(B, A), dscale = 2.f * inv;
   // x[l]: the input of layer l, [B][in_l]; x[L]: the mean; d[l]: [B][out_l]
   std::vector<std::vector<float>> x((size_t)L + 1), d((size_t)L);
   x[0].resize((size_t)B * POLICY_NOBS);
   for (int l = 0; l < L; l++) x[(size_t)l + 1].resize((size_t)B * (size_t)P.out[l]), d[(size_t)l].resize((size_t)B * (size_t)P.out[l]);
-  float sq = 0.f;
   for (int s = 0; s < B; s++) {
     const int64_t p = policy_fit_index(shuffle, (uint32_t)seed, (uint32_t)(seed >> 32), k, (uint32_t)s, (uint32_t)B, n);
     for (int c = 0; c < POLICY_NOBS; c++)
@@ -148,11 +148,7 @@ inline float policy_fit_step_ref(const MmxPolicy& P, float* blob, const float* o
         dst[j] = l + 1 < L ? policy_activate(P.activation, val) : val;
       }
     }
-    for (int a = 0; a < A; a++) {
-      const float mean = x[(size_t)L][(size_t)s * (size_t)A + (size_t)a], y = target[(size_t)p * (size_t)A + (size_t)a], e = mean - y;
-      sq = fmaf(e, e, sq);
-      d[(size_t)L - 1][(size_t)s * (size_t)A + (size_t)a] = policy_fit_out_delta(mean, y, dscale);
-    }
+    out_delta(s, p, &x[(size_t)L][(size_t)s * (size_t)A], &d[(size_t)L - 1][(size_t)s * (size_t)A]);
     for (int l = L - 2; l >= 0; l--) {
       const int out = P.out[l], nout = P.out[l + 1];
       const float* w = blob + P.woff[l + 1];
@@ -174,6 +170,21 @@ inline float policy_fit_step_ref(const MmxPolicy& P, float* blob, const float* o
         blob[at] = policy_fit_update(blob[at], g, m + at, v + at, opt);
       }
   }
+}
+// The mean-squared error's step.  Returns the batch loss before the update: the squared errors summed in (s, a)
+// order, one fused chain, times 1 / (B A).
+inline float policy_fit_step_ref(const MmxPolicy& P, float* blob, const float* obs, const float* target, int64_t n, int B,
+                                 int shuffle, uint64_t seed, uint64_t k, const MmxFitOpt& opt, float* m, float* v) {
+  const int A = P.A;
+  const float inv = policy_fit_inv_count(B, A), dscale = 2.f * inv;
+  float sq = 0.f;
+  policy_step_ref(P, blob, obs, n, B, shuffle, seed, k, opt, m, v, [&](int, int64_t p, const float* mean, float* d) {
+    for (int a = 0; a < A; a++) {
+      const float y = target[(size_t)p * (size_t)A + (size_t)a], e = mean[a] - y;
+      sq = fmaf(e, e, sq);
+      d[a] = policy_fit_out_delta(mean[a], y, dscale);
+    }
+  });
   return sq * inv;
 }
 

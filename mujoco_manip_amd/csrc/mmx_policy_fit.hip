@@ -21,13 +21,25 @@
 //
 // No atomics; every sum's order is fixed by (B, the layer sizes) alone.  The workspace (float offsets, B = batch):
 //   x_l [B][in_l] for l = 0 .. L-1, then d_l [B][out_l], then the loss partials [ceil(B / FIT_TS)], then the chunk
-//   partials [ceil(B / FIT_KC)][policy_fit_param_floats].
+//   partials [ceil(B / FIT_KC)][policy_fit_param_floats], then the PG statistics' partials [ceil(B / FIT_TS)][3].
+//
+// The policy-gradient step (mmx_policy_fit_pg; the closed forms: mmx_pg.h) is the same step with another output
+// delta, four launches:
+//   mmx_pg_forward_kernel    the pass above (one text, mmx_fit_forward.inc) with PPO's clipped surrogate: the A output
+//                            threads exchange z and z' through LDS, each forms the samples' ratios and its own delta,
+//                            thread 0 the tile's three statistic partials
+//   mmx_fit_wgrad_kernel, mmx_fit_update_kernel    as they are (no loss_out)
+//   mmx_pg_stats_kernel      one workgroup: the tiles' partials in tile order into stats_out[k][3]
+// and, for mmx_gae: mmx_gae_kernel (one lane per env column, t backward: rows [t][N] read and written coalesced),
+// mmx_pg_moments_kernel (one workgroup of PG_SUM_LANES threads: both sums in pg_sum's shape) and
+// mmx_pg_rescale_kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 
 #include "mmx_launch.h"
+#include "mmx_pg.h"
 #include "mmx_policy_fit.h"
 
 namespace {
@@ -51,129 +63,12 @@ __device__ __forceinline__ size_t fit_d_off(const MmxPolicy& P, int l, int B) {
 }  // namespace
 
 // ------------------------------------------------------------------ forward pass and deltas
-extern "C" __global__ void __launch_bounds__(kThreads)
-mmx_fit_forward_kernel(MmxPolicy P, MmxFit F) {
-  __shared__ __attribute__((aligned(16))) float buf[2][POLICY_MAX_WIDTH * kTS];  // [unit][sample], ping-pong
-  __shared__ int64_t pair[kTS];
-  __shared__ float sq[kTS * POLICY_MAX_ADIM];
-  const int tid = threadIdx.x, B = F.B;
-  const int s0 = (int)blockIdx.x * kTS;
-  const int ns = min(kTS, B - s0);  // the tile's real samples; the others compute on pair 0's data and store nothing
-  const float* data = policy_data(P);
-  const int L = policy_u(P.n_layers), activation = policy_u(P.activation), A = policy_u(P.A);
-
-  if (tid < kTS)
-    pair[tid] = tid < ns ? policy_fit_index(F.shuffle, F.seed_lo, F.seed_hi, F.k, (uint32_t)(s0 + tid), (uint32_t)B, F.n) : 0;
-  __syncthreads();
-  float* x0 = F.ws;  // x_0 [B][85]
-  for (int e = tid; e < kTS * POLICY_NOBS; e += kThreads) {
-    const int s = e / POLICY_NOBS, c = e - s * POLICY_NOBS;
-    const float v = policy_normalise(F.obs[(size_t)pair[s] * POLICY_NOBS + (size_t)c], data[P.shift_off + c], data[P.scale_off + c]);
-    buf[0][c * kTS + s] = v;
-    if (s < ns) x0[(size_t)(s0 + s) * POLICY_NOBS + (size_t)c] = v;
-  }
-  __syncthreads();
-
-  // ---- forward: src -> dst, thread j = neuron j of the layer (its padding neurons, weights 0, give act(0) = 0)
-  size_t xoff = 0, doff = F.d_base;  // x_l and d_l in the workspace, kept current layer by layer
-  int cur = 0;
-  for (int l = 0; l < L; l++) {
-    const int in = policy_u(P.in[l]), out = policy_u(P.out[l]), outp = policy_padded(out);
-    const bool last = l + 1 == L;
-    xoff += (size_t)in * (size_t)B;  // x_{l+1}
-    const float* src = buf[cur];
-    float* dst = buf[cur ^ 1];
-    if (tid < outp) {
-      policy_gptr w = (policy_gptr)(data + policy_u(P.woff[l])) + tid;
-      float acc[kTS];
-      const float bias = data[policy_u(P.boff[l]) + tid];
-#pragma unroll
-      for (int s = 0; s < kTS; s++) acc[s] = bias;
-#pragma unroll 2
-      for (int k = 0; k < in; k++) {
-        const float wk = w[(size_t)k * (size_t)outp];
-        const f32x4* xs = (const f32x4*)(src + k * kTS);
-#pragma unroll
-        for (int q = 0; q < kTS / 4; q++) {
-          const f32x4 xv = xs[q];
-          acc[4 * q + 0] = fmaf(wk, xv.x, acc[4 * q + 0]);
-          acc[4 * q + 1] = fmaf(wk, xv.y, acc[4 * q + 1]);
-          acc[4 * q + 2] = fmaf(wk, xv.z, acc[4 * q + 2]);
-          acc[4 * q + 3] = fmaf(wk, xv.w, acc[4 * q + 3]);
-        }
-      }
-      if (!last) {
-        float* xn = F.ws + xoff;  // x_{l+1} [B][out]
-#pragma unroll
-        for (int s = 0; s < kTS; s++) {
-          const float a = policy_activate(activation, acc[s]);
-          dst[tid * kTS + s] = a;
-          if (s < ns && tid < out) xn[(size_t)(s0 + s) * (size_t)out + (size_t)tid] = a;
-        }
-      } else if (tid < A) {
-        // the output delta into dst, the squared errors for the tile's loss partial
-        float* dl = F.ws + doff;
-#pragma unroll
-        for (int s = 0; s < kTS; s++) {
-          const float y = F.target[(size_t)pair[s] * (size_t)A + (size_t)tid];
-          const float e = acc[s] - y, dv = policy_fit_out_delta(acc[s], y, F.dscale);
-          sq[s * POLICY_MAX_ADIM + tid] = e;
-          dst[tid * kTS + s] = dv;
-          if (s < ns) dl[(size_t)(s0 + s) * (size_t)A + (size_t)tid] = dv;
-        }
-      }
-    }
-    __syncthreads();
-    cur ^= 1;
-    if (!last) doff += (size_t)out * (size_t)B;
-  }
-  if (tid == 0) {
-    float acc = 0.f;
-    for (int s = 0; s < ns; s++)
-      for (int a = 0; a < A; a++) acc = fmaf(sq[s * POLICY_MAX_ADIM + a], sq[s * POLICY_MAX_ADIM + a], acc);
-    F.ws[F.loss_base + blockIdx.x] = acc;
-  }
-
-  // ---- backward: buf[cur] holds d_{l+1} [unit][sample]; thread c = unit c of layer l reads row c of W_{l+1}
-  for (int l = L - 2; l >= 0; l--) {
-    const int out = policy_u(P.out[l]), nout = policy_u(P.out[l + 1]), noutp = policy_padded(nout);
-    const float* src = buf[cur];
-    float* dst = buf[cur ^ 1];
-    xoff -= (size_t)out * (size_t)B;   // x_{l+1} [B][out_l]
-    doff -= (size_t)out * (size_t)B;   // d_l
-    if (tid < out) {
-      policy_gptr w = (policy_gptr)(data + policy_u(P.woff[l + 1])) + (size_t)tid * (size_t)noutp;
-      float acc[kTS];
-#pragma unroll
-      for (int s = 0; s < kTS; s++) acc[s] = 0.f;
-#pragma unroll 2
-      for (int j = 0; j < nout; j++) {
-        const float wj = w[j];
-        const f32x4* ds = (const f32x4*)(src + j * kTS);
-#pragma unroll
-        for (int q = 0; q < kTS / 4; q++) {
-          const f32x4 dv = ds[q];
-          acc[4 * q + 0] = fmaf(wj, dv.x, acc[4 * q + 0]);
-          acc[4 * q + 1] = fmaf(wj, dv.y, acc[4 * q + 1]);
-          acc[4 * q + 2] = fmaf(wj, dv.z, acc[4 * q + 2]);
-          acc[4 * q + 3] = fmaf(wj, dv.w, acc[4 * q + 3]);
-        }
-      }
-      // the saved activation of this unit: x_{l+1}, written above by this very thread
-      const float* xn = F.ws + xoff;
-      float* dl = F.ws + doff;
-#pragma unroll
-      for (int s = 0; s < kTS; s++) {
-        const float a = s < ns ? xn[(size_t)(s0 + s) * (size_t)out + (size_t)tid] : 0.f;
-        const float dv = policy_fit_hidden_delta(activation, acc[s], a);
-        dst[tid * kTS + s] = dv;
-        if (s < ns) dl[(size_t)(s0 + s) * (size_t)out + (size_t)tid] = dv;
-      }
-    }
-    __syncthreads();
-    cur ^= 1;
-  }
-}
+#define FIT_PG 0
+#include "mmx_fit_forward.inc"
+#undef FIT_PG
+#define FIT_PG 1
+#include "mmx_fit_forward.inc"
+#undef FIT_PG
 
 // ------------------------------------------------------------------ weight gradients: X^T D per layer and K chunk
 extern "C" __global__ void __launch_bounds__(kThreads)
@@ -291,5 +186,98 @@ extern "C" hipError_t mmx_launch_policy_fit_step(const MmxPolicy* P, const MmxFi
   hipLaunchKernelGGL(mmx_fit_forward_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, st, *P, *F);
   hipLaunchKernelGGL(mmx_fit_wgrad_kernel, dim3((unsigned)wtiles, (unsigned)chunks, (unsigned)P->n_layers), dim3(kThreads), 0, st, *P, *F);
   hipLaunchKernelGGL(mmx_fit_update_kernel, dim3((unsigned)ublocks), dim3(kThreads), 0, st, *P, *F, *O, blob, m, v, loss_out);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ the policy-gradient step's own launches
+extern "C" __global__ void __launch_bounds__(64)
+mmx_pg_stats_kernel(MmxFit F, MmxPg G, float* stats_out) {
+#pragma clang fp contract(off)
+  const int c = threadIdx.x;  // lane c sums statistic c, the tiles in order
+  if (c >= 3) return;
+  const int tiles = (F.B + kTS - 1) / kTS;
+  const float* sp = F.ws + G.stat_base + c;
+  float acc = 0.f;
+  for (int t = 0; t < tiles; t++) acc += sp[(size_t)t * 3];
+  stats_out[c] = acc * G.invB;
+}
+
+extern "C" size_t mmx_policy_fit_pg_workspace_floats(const MmxPolicy* P, int B, MmxFit* F, MmxPg* G) {
+  const size_t stat_base = (mmx_policy_fit_workspace_floats(P, B, F) + 63) / 64 * 64;
+  if (G) G->stat_base = stat_base;
+  return stat_base + 3 * (((size_t)B + kTS - 1) / kTS);
+}
+
+extern "C" hipError_t mmx_launch_policy_fit_pg_step(const MmxPolicy* P, const MmxFit* F, const MmxPg* G, const MmxFitOpt* O, float* blob,
+                                                    float* m, float* v, float* stats_out, hipStream_t st) {
+  const int B = F->B, tiles = (B + kTS - 1) / kTS, chunks = (B + FIT_KC - 1) / FIT_KC;
+  int wtiles = 1;
+  for (int l = 0; l < P->n_layers; l++) wtiles = std::max(wtiles, (P->in[l] + 1 + 63) / 64 * (policy_padded(P->out[l]) / 64));
+  const int ublocks = (P->shift_off + kThreads - 1) / kThreads + 1;
+  hipLaunchKernelGGL(mmx_pg_forward_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, st, *P, *F, *G);
+  hipLaunchKernelGGL(mmx_fit_wgrad_kernel, dim3((unsigned)wtiles, (unsigned)chunks, (unsigned)P->n_layers), dim3(kThreads), 0, st, *P, *F);
+  hipLaunchKernelGGL(mmx_fit_update_kernel, dim3((unsigned)ublocks), dim3(kThreads), 0, st, *P, *F, *O, blob, m, v, (float*)nullptr);
+  if (stats_out) hipLaunchKernelGGL(mmx_pg_stats_kernel, dim3(1), dim3(64), 0, st, *F, *G, stats_out);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ GAE and the advantages' normalisation
+extern "C" __global__ void __launch_bounds__(kThreads)
+mmx_gae_kernel(float gamma, float gl, int T, int N, const float* __restrict__ reward, const int32_t* __restrict__ done,
+               const float* __restrict__ value, const float* __restrict__ value_last, float* __restrict__ adv_out,
+               float* __restrict__ ret_out) {
+  const int i = (int)blockIdx.x * kThreads + (int)threadIdx.x;  // the env column
+  if (i >= N) return;
+  float adv = 0.f, nv = value_last[i];
+  for (int t = T - 1; t >= 0; t--) {
+    const size_t e = (size_t)t * (size_t)N + (size_t)i;
+    const float val = value[e];
+    float ret;
+    adv = pg_gae_step(gamma, gl, done[3 * e], done[3 * e + 1], reward[e], val, nv, adv, &ret);
+    adv_out[e] = adv;
+    if (ret_out) ret_out[e] = ret;
+    nv = val;  // value[t] is step t - 1's next value
+  }
+}
+
+// one workgroup: moments[0] = the mean, moments[1] = sqrtf(var) + 1e-8f; the sums in pg_sum's shape (mmx_pg.h)
+extern "C" __global__ void __launch_bounds__(PG_SUM_LANES)
+mmx_pg_moments_kernel(const float* __restrict__ x, int64_t n, float* __restrict__ moments) {
+#pragma clang fp contract(off)
+  __shared__ float chain[PG_SUM_LANES];
+  const int tid = threadIdx.x;
+  const float nf = (float)n;
+  float mean = 0.f;
+  for (int square = 0; square < 2; square++) {
+    float acc = 0.f;
+    for (int64_t e = tid; e < n; e += PG_SUM_LANES) acc += pg_sum_term(x[e], mean, square);
+    chain[tid] = acc;
+    __syncthreads();
+    for (int stride = PG_SUM_LANES / 2; stride >= 1; stride >>= 1) {
+      if (tid < stride) chain[tid] += chain[tid + stride];
+      __syncthreads();
+    }
+    const float sum = chain[0];
+    __syncthreads();  // chain is written again by the second pass
+    if (!square) mean = sum / nf;
+    else if (tid == 0) moments[0] = mean, moments[1] = pg_norm_denominator(sum, nf);
+  }
+}
+extern "C" __global__ void __launch_bounds__(kThreads)
+mmx_pg_rescale_kernel(float* __restrict__ x, int64_t n, const float* __restrict__ moments) {
+  const int64_t e = (int64_t)blockIdx.x * kThreads + (int64_t)threadIdx.x;
+  if (e < n) x[e] = pg_normalise(x[e], moments[0], moments[1]);
+}
+
+extern "C" hipError_t mmx_launch_gae(float gamma, float gl, int T, int N, const float* reward, const int32_t* done, const float* value,
+                                     const float* value_last, float* adv_out, float* ret_out, float* moments, hipStream_t st) {
+  hipLaunchKernelGGL(mmx_gae_kernel, dim3((unsigned)((N + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, gamma, gl, T, N, reward, done,
+                     value, value_last, adv_out, ret_out);
+  if (moments) {  // normalise
+    const int64_t n = (int64_t)T * (int64_t)N;
+    hipLaunchKernelGGL(mmx_pg_moments_kernel, dim3(1), dim3(PG_SUM_LANES), 0, st, (const float*)adv_out, n, moments);
+    hipLaunchKernelGGL(mmx_pg_rescale_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, adv_out, n,
+                       (const float*)moments);
+  }
   return hipGetLastError();
 }

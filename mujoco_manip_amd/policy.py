@@ -36,6 +36,44 @@ def _f32(a, name: str, shape=None):
     return np.ascontiguousarray(a)
 
 
+def _fit_config(steps, batch, lr, betas, eps, optimizer, shuffle, seed, reset_optimizer):
+    """(steps, mmx_fit_config) of fit's and fit_pg's common arguments, validated."""
+    if optimizer not in _lib.FIT_OPTIMIZERS:
+        raise ValueError(f"optimizer must be one of {_lib.FIT_OPTIMIZERS}, got '{optimizer}'")
+    steps, batch = int(steps), int(batch)
+    if steps < 0:
+        raise ValueError(f"steps must be >= 0, got {steps}")
+    if not 1 <= batch <= _lib.FIT_MAX_BATCH:
+        raise ValueError(f"batch must be in 1 .. {_lib.FIT_MAX_BATCH}, got {batch}")
+    b1, b2 = (float(v) for v in betas)
+    if not (np.isfinite(lr) and lr > 0 and np.isfinite(eps) and eps > 0 and 0 <= b1 < 1 and 0 <= b2 < 1):
+        raise ValueError("lr and eps must be finite and > 0, betas in [0, 1)")
+    return steps, _lib.MMXFitConfig(optimizer=_lib.FIT_OPTIMIZERS.index(optimizer), batch=batch, shuffle=int(bool(shuffle)),
+                                    reset_optimizer=int(bool(reset_optimizer)), lr=lr, beta1=b1, beta2=b2, eps=eps,
+                                    seed=int(seed) & (2**64 - 1))
+
+
+def _check_rows(env, tensors) -> int:
+    """n, given that every (name, tensor, width) is a contiguous float32 torch tensor [n, width] ([n] at width 0) on
+    the env's device with the same n in 1 .. 2^31 - 1."""
+    import torch
+
+    for name, t, width in tensors:
+        shape = f"[n, {width}]" if width else "[n]"
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor on {env.device}")
+        if t.dtype != torch.float32 or t.dim() != (2 if width else 1) or (width and t.shape[1] != width):
+            raise ValueError(f"{name} must be float32 {shape}, got {t.dtype} {tuple(t.shape)}")
+        if t.device != torch.device(env.device):
+            raise ValueError(f"{name} must be on {env.device}, got {t.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    rows = [t.shape[0] for _, t, _ in tensors]
+    if len(set(rows)) != 1 or not 1 <= rows[0] < 2**31:
+        raise ValueError(f"{', '.join(n for n, _, _ in tensors)} must have the same number of rows in 1 .. 2^31 - 1, got {rows}")
+    return rows[0]
+
+
 class MlpPolicy:
     def __init__(self, layers, activation: str = "tanh", obs_shift=None, obs_scale=None, log_std=None, low=None,
                  high=None, seed: int = 0):
@@ -142,31 +180,8 @@ class MlpPolicy:
         import torch
 
         dev, env = self.device_policy, self._env
-        if optimizer not in _lib.FIT_OPTIMIZERS:
-            raise ValueError(f"optimizer must be one of {_lib.FIT_OPTIMIZERS}, got '{optimizer}'")
-        steps, batch = int(steps), int(batch)
-        if steps < 0:
-            raise ValueError(f"steps must be >= 0, got {steps}")
-        if not 1 <= batch <= _lib.FIT_MAX_BATCH:
-            raise ValueError(f"batch must be in 1 .. {_lib.FIT_MAX_BATCH}, got {batch}")
-        for name, t, width in (("obs", obs, _lib.NOBS), ("target", target, self.action_dim)):
-            if not isinstance(t, torch.Tensor):
-                raise ValueError(f"{name} must be a torch tensor on {env.device}")
-            if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != width:
-                raise ValueError(f"{name} must be float32 [n, {width}], got {t.dtype} {tuple(t.shape)}")
-            if t.device != torch.device(env.device):
-                raise ValueError(f"{name} must be on {env.device}, got {t.device}")
-            if not t.is_contiguous():
-                raise ValueError(f"{name} must be contiguous")
-        n = obs.shape[0]
-        if target.shape[0] != n or not 1 <= n < 2**31:
-            raise ValueError(f"obs and target must have the same number of rows in 1 .. 2^31 - 1, got {n} and {target.shape[0]}")
-        b1, b2 = (float(v) for v in betas)
-        if not (np.isfinite(lr) and lr > 0 and np.isfinite(eps) and eps > 0 and 0 <= b1 < 1 and 0 <= b2 < 1):
-            raise ValueError("lr and eps must be finite and > 0, betas in [0, 1)")
-        cfg = _lib.MMXFitConfig(optimizer=_lib.FIT_OPTIMIZERS.index(optimizer), batch=batch, shuffle=int(bool(shuffle)),
-                                reset_optimizer=int(bool(reset_optimizer)), lr=lr, beta1=b1, beta2=b2, eps=eps,
-                                seed=int(seed) & (2**64 - 1))
+        steps, cfg = _fit_config(steps, batch, lr, betas, eps, optimizer, shuffle, seed, reset_optimizer)
+        n = _check_rows(env, (("obs", obs, _lib.NOBS), ("target", target, self.action_dim)))
         loss = torch.empty(steps, dtype=torch.float32, device=env.device)
         if steps:
             with env.sim._on_sim_stream(env.device) as (cur, sst):
@@ -174,6 +189,47 @@ class MlpPolicy:
                     t.record_stream(sst)
                 dev.fit(obs.data_ptr(), target.data_ptr(), n, steps, cfg, loss.data_ptr())
         return loss
+
+    # ------------------------------------------------------------------ policy gradients (mmx_policy_fit_pg)
+    def fit_pg(self, obs, mean_old, noise, adv, steps: int, clip: float = 0.2, batch: int = 8192, lr: float = 3e-4,
+               betas=(0.9, 0.999), eps: float = 1e-8, optimizer: str = "adam", shuffle: bool = True, seed: int = 0,
+               reset_optimizer: bool = False):
+        """`steps` minibatch steps of PPO's clipped surrogate -mean(min(r adv, clip(r, 1 - clip, 1 + clip) adv)) on
+        the samples of a rollout: obs [n, 85] (what each step was given), mean_old and noise [n, A] (the rollout's
+        record of that name), adv [n] (PickPlaceVecEnv.gae); contiguous float32 torch tensors on the policy's
+        device.  r is the ratio of the policy's density now to the one at the rollout, of the sample before the
+        clamp; log_std is not trained (set_log_std schedules it).  Updates the weights in place on the env's stream
+        like fit, with which it shares the optimiser's moments and step count.  Returns the statistics [steps, 3]
+        (a device tensor): per step, before its update, the surrogate loss, the approximate KL mean((r - 1) - log r)
+        and the fraction of samples the clip removed from the gradient."""
+        import torch
+
+        dev, env = self.device_policy, self._env
+        steps, cfg = _fit_config(steps, batch, lr, betas, eps, optimizer, shuffle, seed, reset_optimizer)
+        n = _check_rows(env, (("obs", obs, _lib.NOBS), ("mean_old", mean_old, self.action_dim), ("noise", noise, self.action_dim),
+                              ("adv", adv, 0)))
+        if not (np.isfinite(clip) and 0 < clip < 1):
+            raise ValueError(f"clip must be in (0, 1), got {clip}")
+        if self.log_std is None:
+            raise ValueError("fit_pg needs a stochastic policy (log_std): a deterministic one has no likelihood ratio")
+        stats = torch.empty((steps, 3), dtype=torch.float32, device=env.device)
+        if steps:
+            with env.sim._on_sim_stream(env.device) as (cur, sst):
+                for t in (obs, mean_old, noise, adv, stats):
+                    t.record_stream(sst)
+                dev.fit_pg(obs.data_ptr(), mean_old.data_ptr(), noise.data_ptr(), adv.data_ptr(), n, steps,
+                           _lib.MMXPgConfig(fit=cfg, clip=float(clip)), stats.data_ptr())
+        return stats
+
+    def set_log_std(self, log_std):
+        """Sets the bound policy's log_std [A] in place (waits for the env's stream); the next rollout draws
+        its actions with exp(log_std).  Nothing else of the policy changes."""
+        dev = self.device_policy
+        log_std = _f32(log_std, "log_std", (self.action_dim,))
+        if not np.isfinite(log_std).all():
+            raise ValueError("log_std must be finite")
+        dev.set_log_std(log_std)
+        self.log_std = log_std
 
     def weights(self):
         """[(W [out, in], b [out]), ...] numpy arrays (torch layout) of the bound policy's weights as they are now;
@@ -217,3 +273,33 @@ class MlpPolicy:
         if self._dev is not None:
             self._dev.close()
         self._dev = self._env = None
+
+
+class MlpCritic(MlpPolicy):
+    """A value network V(obs): an MlpPolicy whose last layer has width 1, with no log_std and no action box.  eval
+    gives V [n, 1] and fit regresses it to targets [n, 1] (PickPlaceVecEnv.gae's returns); it is never rolled out.
+
+        critic = MlpCritic.from_torch(vnet, obs_shift=mu, obs_scale=1 / sd).bind(env)
+        value = critic.eval(obs.reshape(-1, 85)).reshape(T, N)
+        adv, ret = env.gae(rec["reward"], rec["done"], value, critic.eval(env_obs)[:, 0])
+        critic.fit(obs.reshape(-1, 85), ret.reshape(-1, 1), steps=10)
+    """
+
+    def __init__(self, layers, activation: str = "tanh", obs_shift=None, obs_scale=None, seed: int = 0):
+        super().__init__(layers, activation=activation, obs_shift=obs_shift, obs_scale=obs_scale, seed=seed)
+        if self.action_dim != 1:
+            raise ValueError(f"a critic's last layer has 1 output, got {self.action_dim}")
+
+    def bind(self, env) -> "MlpCritic":
+        """Create the device object on the env's device, whatever the env's action dimension: no box, no clamp."""
+        self.close()
+        self._dev = _lib.Policy(env.sim, self.layers, ACTIVATIONS.index(self.activation), self.obs_shift, self.obs_scale,
+                                None, None, None, self.seed)
+        self._env = env
+        return self
+
+    def fit_pg(self, *args, **kw):
+        raise TypeError("a critic has no policy gradient: fit it on the returns with fit()")
+
+    def set_log_std(self, log_std):
+        raise TypeError("a critic has no log_std")

@@ -33,6 +33,26 @@ def split_obs(flat: torch.Tensor) -> dict:
     return {k: flat[..., a:b].reshape(*flat.shape[:-1], *shape) for k, (a, b, shape) in OBS_SLICES.items()}
 
 
+def check_gae_args(reward, done, value, value_last, gamma, lam, device):
+    """What PickPlaceVecEnv.gae asks of its arguments, before the library is touched."""
+    device = torch.device(device)
+    if not (isinstance(reward, torch.Tensor) and reward.dim() == 2 and reward.shape[1] >= 1):
+        raise ValueError("reward must be a torch tensor [T, N] with N >= 1")
+    T, N = reward.shape
+    if T * N >= 2**31:
+        raise ValueError(f"reward has {T * N} entries; gae takes at most 2^31 - 1")
+    for name, t, shape, dtype in (("reward", reward, (T, N), torch.float32), ("done", done, (T, N, 3), torch.int32),
+                                  ("value", value, (T, N), torch.float32), ("value_last", value_last, (N,), torch.float32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be a {dtype} torch tensor of shape {shape}")
+        if t.device != device:
+            raise ValueError(f"{name} must be on {device}, got {t.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    if not (0.0 <= float(gamma) <= 1.0 and 0.0 <= float(lam) <= 1.0):  # (a NaN fails both)
+        raise ValueError(f"gamma and lam must be in [0, 1], got {gamma} and {lam}")
+
+
 class Snapshot:
     """The state of `num_envs` environments on the device (PickPlaceVecEnv.snapshot): `data` is the uint8
     tensor [num_envs, rec_bytes] of their records (include/mmx_api.h; _lib.snapshot_field_offsets gives
@@ -263,6 +283,25 @@ class PickPlaceVecEnv:
         dev.rollout_dagger(self.sim, T, call, _lib.MMXDaggerConfig(beta=beta, takeover_dist=takeover_dist), drec, rec)
         self._last_action = out["actions"]
         return out
+
+    # ------------------------------------------------------------------ advantages (mmx_gae)
+    def gae(self, reward, done, value, value_last, gamma: float = 0.99, lam: float = 0.95, normalize: bool = False):
+        """Generalised advantage estimation over a rollout record, on the env's stream: reward [T, N] float32, done
+        [T, N, 3] int32 (a rollout's record), value [T, N] = V of the observation each step was given, value_last
+        [N] = V of the observation after the last step (contiguous tensors on the env's device; N need not be
+        num_envs).  Returns (adv, ret), both [T, N]: ret = adv + value before `normalize` rescales adv to mean 0 and
+        variance 1 over all T N entries.  A terminated or truncated step takes next value 0 and cuts the recursion."""
+        check_gae_args(reward, done, value, value_last, gamma, lam, self.device)
+        T, N = reward.shape
+        adv, ret = torch.empty_like(reward), torch.empty_like(reward)
+        if T:
+            cfg = _lib.MMXGaeConfig(gamma=float(gamma), lambda_=float(lam), normalize=int(bool(normalize)))
+            with self.sim._on_sim_stream(self.device) as (cur, sst):
+                for t in (reward, done, value, value_last, adv, ret):
+                    t.record_stream(sst)
+                self.sim.gae(cfg, T, N, reward.data_ptr(), done.data_ptr(), value.data_ptr(), value_last.data_ptr(),
+                             adv.data_ptr(), ret.data_ptr())
+        return adv, ret
 
     # ------------------------------------------------------------------ snapshot / restore
     def snapshot(self) -> Snapshot:
