@@ -5,12 +5,10 @@ decodes it (PIL verifies each chunk's CRC-32), zlib inflates the IDAT stream (ve
 Adler-32) to the filter-0 scanlines, and the chunk layout is walked by hand.  Inputs: random
 (incompressible) images, flat and striped ones (long matches at both distances), rendered camera
 images, and sizes that are not multiples of 16 or not square."""
-import io
-import struct
-import zlib
-
 import numpy as np
 import pytest
+
+from png_ref import round_trip
 
 torch = pytest.importorskip("torch")
 
@@ -28,39 +26,11 @@ def sim():
     s.close()
 
 
-def _chunks(png: bytes):
-    assert png[:8] == b"\x89PNG\r\n\x1a\n"
-    k, out = 8, []
-    while k < len(png):
-        n = struct.unpack(">I", png[k:k + 4])[0]
-        typ, data = png[k + 4:k + 8], png[k + 8:k + 8 + n]
-        crc = struct.unpack(">I", png[k + 8 + n:k + 12 + n])[0]
-        assert zlib.crc32(typ + data) & 0xFFFFFFFF == crc, typ
-        out.append((typ, data))
-        k += 12 + n
-    assert k == len(png)
-    return out
-
-
 def _check(sim, imgs: np.ndarray):
-    from PIL import Image
-
     packed, offs = sim.png_encode(torch.as_tensor(imgs).cuda())
     data = packed.cpu().numpy().tobytes()
-    sizes = []
-    for i, im in enumerate(imgs):
-        png = data[offs[i]:offs[i + 1]]
-        ch = _chunks(png)
-        assert ch[0][0] == b"IHDR" and ch[-1][0] == b"IEND"
-        w, h = struct.unpack(">II", ch[0][1][:8])
-        assert (h, w) == im.shape[:2] and ch[0][1][8:] == b"\x08\x02\x00\x00\x00"
-        raw = zlib.decompress(b"".join(d for t, d in ch if t == b"IDAT"))
-        lines = np.frombuffer(raw, np.uint8).reshape(h, 3 * w + 1)
-        assert (lines[:, 0] == 0).all()
-        np.testing.assert_array_equal(lines[:, 1:].reshape(im.shape), im)
-        np.testing.assert_array_equal(np.asarray(Image.open(io.BytesIO(png)).convert("RGB")), im)
-        sizes.append(len(png))
-    return np.array(sizes)
+    # per file: the chunk walk with its CRC-32s, zlib to the filter-0 scanlines, PIL to the pixels (png_ref.round_trip)
+    return np.array([round_trip(data[offs[i]:offs[i + 1]], im) for i, im in enumerate(imgs)])
 
 
 def test_png_random_and_structured(sim):
